@@ -10,7 +10,14 @@ passes).  Multi-GPU: one process per GPU, z-planes sharded across ranks (weak
 scaling: 64 planes per rank, the global sweep grows with N), no data-path collective;
 a barrier + synchronize bracket the timed region and the max time over ranks counts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the per-kernel and
+roofline figures in it come from HIP events on the timed steps themselves).  ``--dump-outputs DIR``
+also writes a fixed sample of what the last timed step computed as DIR/<name>.npy.  ``--full`` adds
+everything that takes runs of its own: the output checks against the reference's fp64 signatures
+(exit 3 on a mismatch), the cfg3 / cfg4 / cfg5 secondary lines, the per-rank shares and the CPU
+baseline.
 """
 import argparse
 import contextlib
@@ -604,6 +611,31 @@ def check_plane(plane, z):
     return r
 
 
+DUMP_POINTS = 1 << 16  # per plane: 64 planes x 65,536 points x (re, im) fp32 = 32 MiB
+DUMP_SEED = 20
+
+
+def dump_pixels():
+    """The flat pixel indices [DUMP_POINTS] of a plane that --dump-outputs keeps: distinct, the same in
+    every run (the first DUMP_POINTS of a seeded CPU permutation of the N x N pixels)."""
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    return torch.randperm(N_FIELD * N_FIELD, generator=g)[:DUMP_POINTS].clone()
+
+
+def dump_outputs(out, dirname, rank, world):
+    """--dump-outputs: the planes the last timed step wrote (``out`` [Z, 1, 1, N, N] complex64, what
+    a caller of asm_apply receives), sampled at DUMP_POINTS distinct pixels of every plane -- the
+    whole 8.6 GB does not fit a file.  The pixel indices are the head of a permutation drawn by a CPU
+    generator seeded with DUMP_SEED (dump_pixels), so every run and every build samples the same pixels.  Written as float32 [Z, DUMP_POINTS, 2]
+    (re, im) to DIR/cfg2_planes.npy (DIR/cfg2_planes_rank<r>.npy with more than one rank)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    idx = dump_pixels().to(out.device)
+    sample = torch.view_as_real(out.reshape(out.shape[0], -1).index_select(1, idx)).float().cpu().numpy()
+    name = "cfg2_planes.npy" if world == 1 else f"cfg2_planes_rank{rank}.npy"
+    np.save(os.path.join(dirname, name), sample)
+
+
 class Ranks:
     """One process per GPU (torch.distributed.run sets RANK / LOCAL_RANK / WORLD_SIZE): the barrier and
     the max-over-ranks reduction of the timed region.  ``dry_run``: every rank on the CPU over gloo,
@@ -763,10 +795,10 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--z-chunk", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-planes", type=int, default=64, help="cpu_baseline sample size (whole 4096^2 planes)")
     ap.add_argument("--cpu-budget", type=float, default=30.0, help="cpu_baseline time budget, seconds")
-    ap.add_argument("--headline-only", action="store_true", help="skip the cfg3 / cfg4 / cfg5 secondary measurements")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: skip the cfg3 / cfg4 / cfg5 secondary measurements")
     ap.add_argument("--secondary-timeout", type=float, default=420.0,
                     help="seconds the cfg3 / cfg4 / cfg5 secondaries may take before the line is printed without them")
     ap.add_argument("--cpu-only", action="store_true",
@@ -774,10 +806,19 @@ def main():
     ap.add_argument("--cfg2-split", choices=("weak", "strong"), default="weak",
                     help="weak: 64 z-planes per rank (the default line); strong: the 64-plane sweep split over the ranks")
     ap.add_argument("--no-shares", action="store_true",
-                    help="skip the one-GPU timing of the per-rank shares of an 8-GPU run (world size 1 only)")
+                    help="with --full: skip the one-GPU timing of the per-rank shares of an 8-GPU run (world size 1 only)")
     ap.add_argument("--dry-run", action="store_true",
                     help="rehearse the rank orchestration on the CPU (gloo, propagation stubbed, no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the output checks against the reference's signatures, "
+                         "the cfg3 / cfg4 / cfg5 secondaries, the per-rank shares and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the last step's output planes to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.dry_run or args.cpu_only):
+        ap.error("--dump-outputs writes the GPU path's output: not with --dry-run or --cpu-only")
     if args.cpu_only:
         print(json.dumps({"cpu_baseline": cpu_baseline(args.cpu_budget, args.cpu_planes, progress=True)}))
         return
@@ -826,10 +867,14 @@ def main():
     elapsed = timed(step, args.steps, args.warmup, ranks, on_start=start_timing)
     _lib.timing_enable(False)
     kern = {k: _lib.timing_read(k) for k in ("asm_rows_fwd", "asm_cols", "asm_rows_inv")}
-    # self-check outside the timed region: this rank's first plane (z = 20 mm on rank 0) and, when
-    # it is in this rank's share, the sweep's last (120 mm), vs the reference's fp64 signature
-    checks = [c for c in (check_plane(out[0, 0, 0], zs[0]), check_plane(out[-1, 0, 0], zs[-1])) if c]
-    checks_ok = all(ranks.gather(all(c["ok"] for c in checks)))
+    if args.dump_outputs:
+        dump_outputs(out, args.dump_outputs, rank, world)
+    # --full: self-check outside the timed region: this rank's first plane (z = 20 mm on rank 0) and,
+    # when it is in this rank's share, the sweep's last (120 mm), vs the reference's fp64 signature
+    checks, checks_ok = None, True
+    if args.full:
+        checks = [c for c in (check_plane(out[0, 0, 0], zs[0]), check_plane(out[-1, 0, 0], zs[-1])) if c]
+        checks_ok = all(ranks.gather(all(c["ok"] for c in checks)))
 
     planes = total_planes * args.steps
     value = planes / elapsed
@@ -907,9 +952,9 @@ def main():
         "roofline_by_kernel": {k: round(v["gbs_pruned"] / HBM_PEAK_GBS, 4) for k, v in stats.items()},
         "roofline_step": roof_step,
         "roofline_survey_model": roof_model,
-        "output_check": {"ok": checks_ok, "planes": checks},
+        "output_check": {"ok": checks_ok, "planes": checks} if args.full else None,
     }
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         # secondary workloads never take the headline line down with them: an exception is reported
         # in the line, and a secondary still running after --secondary-timeout seconds (a hang, e.g.
         # in a collective) is reported as such by a watchdog that prints the line and ends every rank
@@ -939,7 +984,7 @@ def main():
                 snapshot[0] = dict(secondary)
             watchdog.cancel()
         line["secondary"] = secondary
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.cpu_budget, args.cpu_planes)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -21,8 +21,8 @@ for f in sorted(glob.glob(os.path.join(sys.argv[1], "bench_*.json"))):
 PY
 }
 for i in 1 2; do
-  timeout -k 10 240 python -u bench.py --headline-only --no-cpu-baseline --steps 20 --warmup 3 > $OUT/bench_a$i.json 2> $OUT/bench_a$i.err &&
-  THZDOE_LIB=$PWD/$B timeout -k 10 240 python -u bench.py --headline-only --no-cpu-baseline --steps 20 --warmup 3 > $OUT/bench_b$i.json 2> $OUT/bench_b$i.err || { summary; exit 1; }
+  timeout -k 10 240 python -u bench.py --full --headline-only --no-cpu-baseline --steps 20 --warmup 3 > $OUT/bench_a$i.json 2> $OUT/bench_a$i.err &&
+  THZDOE_LIB=$PWD/$B timeout -k 10 240 python -u bench.py --full --headline-only --no-cpu-baseline --steps 20 --warmup 3 > $OUT/bench_b$i.json 2> $OUT/bench_b$i.err || { summary; exit 1; }
 done
 summary
 timeout -k 10 900 python -u -m pytest -q --timeout 300 --timeout-method thread -m gpu $TESTS > $OUT/tests_a.log 2>&1

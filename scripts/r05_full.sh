@@ -11,7 +11,7 @@ tail -3 $O/tests.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit $?
 tail -2 $O/smoke.log
-timeout -k 10 900 python3 -u bench.py > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 900 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
 tail -c 600 $O/bench.json
 bash scripts/profile_asm.sh gpurun_out/${2:-r05_prof2} || exit $?
 bash scripts/r05_small_traces.sh gpurun_out/${3:-r05_small2} || exit $?

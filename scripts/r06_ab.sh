@@ -27,7 +27,7 @@ if [ -n "$TESTS" ]; then
   [ $rc -eq 0 ] || exit $rc
 fi
 for i in 1 2; do
-  env $ENVA timeout -k 10 240 python -u bench.py --headline-only --no-cpu-baseline --steps 20 --warmup 3 > $OUT/bench_a$i.json 2> $OUT/bench_a$i.err &&
-  env $ENVB timeout -k 10 240 python -u bench.py --headline-only --no-cpu-baseline --steps 20 --warmup 3 > $OUT/bench_b$i.json 2> $OUT/bench_b$i.err || { summary; exit 1; }
+  env $ENVA timeout -k 10 240 python -u bench.py --full --headline-only --no-cpu-baseline --steps 20 --warmup 3 > $OUT/bench_a$i.json 2> $OUT/bench_a$i.err &&
+  env $ENVB timeout -k 10 240 python -u bench.py --full --headline-only --no-cpu-baseline --steps 20 --warmup 3 > $OUT/bench_b$i.json 2> $OUT/bench_b$i.err || { summary; exit 1; }
 done
 summary

@@ -17,7 +17,7 @@ if [ "$PART" = A ]; then
   [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
   timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit $?
   tail -2 $O/smoke.log
-  timeout -k 10 600 python3 -u bench.py > $O/bench.json 2> $O/bench.err || exit $?
+  timeout -k 10 600 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
   tail -c 400 $O/bench.json
 else
   [ "$PART" = C ] || bash scripts/profile_asm.sh $O/prof || exit $?

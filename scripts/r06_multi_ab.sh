@@ -10,7 +10,7 @@ for pass in 1 2; do
   i=0
   for E in "$@"; do
     i=$((i+1))
-    env $E timeout -k 10 240 python -u bench.py --headline-only --no-cpu-baseline --steps 20 --warmup 3 \
+    env $E timeout -k 10 240 python -u bench.py --full --headline-only --no-cpu-baseline --steps 20 --warmup 3 \
       > $OUT/bench_v${i}_p$pass.json 2> $OUT/bench_v${i}_p$pass.err || { echo "FAILED: $E"; exit 1; }
     python - $OUT/bench_v${i}_p$pass.json "$E" <<'PY'
 import json, sys

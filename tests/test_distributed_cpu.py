@@ -318,6 +318,19 @@ def test_bench_refuses_gpus_world_mismatch():
     assert r.returncode == 2 and "WORLD_SIZE" in r.stderr
 
 
+def test_bench_dump_outputs_refuses_the_dry_run_and_zero_steps():
+    """--dump-outputs writes what the GPU path computed, so the CPU rehearsal refuses it; --steps
+    sets the number of timed steps, so it must be at least 1 (argparse usage errors, exit 2)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for extra, word in ((["--dump-outputs", "unused_dir"], "--dump-outputs"), (["--steps", "0"], "--steps")):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dry-run"] + extra,
+                           capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 2 and word in r.stderr, r.stderr[-2000:]
+    assert not os.path.exists(os.path.join(root, "unused_dir"))
+
+
 def test_bench_secondary_watchdog_prints_the_line_and_exits_nonzero():
     """A secondary that hangs (e.g. in a collective) must not cost the headline line: the watchdog
     prints the line with the finished secondaries (the snapshot the main thread published) and the
