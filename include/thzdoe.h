@@ -53,13 +53,13 @@ typedef void* thz_stream_t; /* hipStream_t */
  * rng / rng_stream to thz_doe_desc and thz_quant_desc; 4 added thz_asm_transfer_function and
  * thz_rs_kernel, which the bindings require; 5 appended thz_asm_desc.window_mask, 6 thz_asm_desc.z_dev,
  * 7 added thz_doe_quant_backward and thz_radial_quant_backward, 8 thz_step_fetch and
- * thz_adam_step):
+ * thz_adam_step, 9 thz_asm_slice_workspace_size and thz_asm_slice_forward):
  * a caller compares thz_abi_version()
  * with the THZ_ABI_VERSION it was compiled against before its first call, since a shorter
  * struct from an older header would make the library read past it.  Descriptors are plain C
  * structs: zero-initialise them (memset / `= {0}` / ctypes defaults) so fields a caller does not
  * know about stay 0 (no noise buffer and no device generator means no noise). */
-#define THZ_ABI_VERSION 8
+#define THZ_ABI_VERSION 9
 
 /* Library identity. */
 const char* thz_version(void);
@@ -116,6 +116,26 @@ typedef struct thz_asm_desc {
 int thz_asm_workspace_size(const thz_asm_desc* d, size_t* bytes);
 int thz_asm_forward(const thz_asm_desc* d, const void* in, void* out, void* workspace, size_t workspace_bytes,
                     thz_stream_t stream);
+/*
+ * z-x slice: one output row of every plane of a z-sweep, without forming the planes -- the axial
+ * map of experiment_extend_depth_of_focus.ipynb:229-263 (cell Submm_Setup_test.forward: for each z
+ * of prop_range = np.linspace(20 mm, 120 mm, num=200) it propagates the whole plane and keeps
+ * final_field.data[0, 0, 49, :], stacked into fields_zx).
+ *   in [B, C, H, W] -> out [Z, B, C, Wo] == thz_asm_forward's out[:, :, :, row, :]
+ * row indexes the output grid, 0 <= row < Ho (Ho = H when unpad is set, else the padded height).
+ * The row pass runs as in thz_asm_forward; the column pass folds exp(2 pi i m R / Ph) of the padded
+ * row R into the column spectrum once and then sums spectrum x H_z per plane (no inverse column
+ * transform, no per-plane intermediate of height Ho); one Pw-point inverse row transform per
+ * (z, b, c).  Forward only, host z[] only, no window mask: adjoint != 0, z_dev != NULL and
+ * window_mask != NULL return THZ_E_UNSUPPORTED, as does a padded height H + 2 pad_h other than
+ * 1024, 2048, 4096, 8192 or 16384 (slice thz_asm_forward's planes there); a bad row or a null
+ * pointer THZ_E_ARG; a short workspace THZ_E_WORKSPACE -- all before any device call.
+ * Workspace: T as above and V [zc][BC][ncols] complex64, the column sums of zc = min(64, the forward's
+ * z-chunk) planes at a time (the plane recurrence restarts with every chunk, as in thz_asm_forward).
+ */
+int thz_asm_slice_workspace_size(const thz_asm_desc* d, size_t* bytes);
+int thz_asm_slice_forward(const thz_asm_desc* d, int row, const void* in, void* out /* [Z,B,C,Wo] */,
+                          void* workspace, size_t workspace_bytes, thz_stream_t stream);
 /* Plan facts for diagnostics / bench byte counts: number of spectral columns the kernels
  * keep (|m_y| <= J; ncols = 2J+1, or Pw when nothing is cut) and z-planes per column pass. */
 int thz_asm_band(const thz_asm_desc* d, int* ncols, int* z_chunk);
@@ -490,7 +510,8 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * Per-kernel HIP-event timing used by bench.py (not part of the reference): when
  * enabled every kernel launch is bracketed by two events on its own stream;
  * thz_timing_read() synchronises on the pending events and returns the summed
- * duration and launch count for one kernel name ("asm_rows_fwd", "asm_cols", ...).
+ * duration and launch count for one kernel name ("asm_rows_fwd", "asm_cols", "asm_rows_inv"; the
+ * z-x slice: "asm_rows_fwd", "asm_cols_slice", "asm_rows_slice"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

@@ -244,14 +244,19 @@ class ASM_prop(nn.Module):
                 out = _prop.asm_propagate(x, wl, sp, zs, ph, pw, unpad=unpad, bandlimit=bl, mask=out_mask,
                                           z_dev=z_dev)
         except RuntimeError as err:
-            print("##################################################")
-            print("An error occurred.  If the error was due to insufficient memory, try decreasing the size of the "
-                  "input field or the size of the padding (i.e. decrease 'padding_scale').")
-            print("For the best results (e.g. to avoid convolution edge artifacts), the support of the input field "
-                  "should be at most 1/2 the size of the input field after padding.")
-            print("##################################################")
+            self._oom_hint()
             raise err
         return out
+
+    @staticmethod
+    def _oom_hint():
+        """The reference's hint on a RuntimeError (Props/ASM_Prop.py:363-370)."""
+        print("##################################################")
+        print("An error occurred.  If the error was due to insufficient memory, try decreasing the size of the "
+              "input field or the size of the padding (i.e. decrease 'padding_scale').")
+        print("For the best results (e.g. to avoid convolution edge artifacts), the support of the input field "
+              "should be at most 1/2 the size of the input field after padding.")
+        print("##################################################")
 
     def forward(self, field: ElectricField) -> ElectricField:
         """pad -> ft2 -> x H -> ift2 -> crop (Props/ASM_Prop.py:314-378), on the MI355X kernels.
@@ -303,3 +308,71 @@ class ASM_prop(nn.Module):
         for k in range(0, len(zs), _prop._lib.THZ_MAX_Z):
             outs.append(self._run(field, zs[k:k + _prop._lib.THZ_MAX_Z]))
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+    def propagate_zx(self, field: ElectricField, z_list, row=None, axis="x") -> torch.Tensor:
+        """Additive API: one output row of every plane of ``z_list`` -> [Z, B, C, Wo], equal to
+        ``propagate_planes(field, z_list)[..., row, :]`` -- the z-x map of the extend-DOF notebook
+        (experiment_extend_depth_of_focus.ipynb:229-263 keeps ``final_field.data[0, 0, 49, :]`` of
+        each of 200 planes).  ``row`` indexes the output grid (the padded plane with
+        ``do_unpad_after_pad=False``); None is the centre row Ho // 2.  ``axis="y"`` returns the
+        output column ``row`` instead, [Z, B, C, Ho].  ``z_list`` may have any length.
+
+        For a complex64 field whose padded height is 1024 ... 16384 (a power of two) the slice
+        kernels run (thz_asm_slice_forward): nothing of the size of a plane per z is allocated.
+        ``axis="y"`` runs them on the transposed field with dx / dy and the paddings exchanged (one
+        transpose of the input); the reference's band limits take both frequency steps from the
+        padded height, so that holds for a square padded plane or with no band limit.  Every other
+        input -- another padded height, a complex128 field, a pending fused DOE modulation, an input
+        that requires grad (the slice kernels have no adjoint) -- propagates the full planes in
+        z-chunks whose temporary stays under 10 GiB and slices each chunk, differentiably."""
+        if axis not in ("x", "y"):
+            raise ValueError(f"propagate_zx: axis must be 'x' or 'y', got {axis!r}")
+        zs = _z_host(z_list)
+        pend = field._take_pending()
+        data = pend.field if pend is not None else field.data
+        B, C, H, W = data.shape
+        ph, pw = self.compute_padding(H, W, return_size_of_padding=True)
+        Ph, Pw = H + 2 * ph, W + 2 * pw
+        unpad = (not self.do_padding) or self.do_unpad_after_pad
+        Ho, Wo = (H, W) if unpad else (Ph, Pw)
+        n = Ho if axis == "x" else Wo
+        if row is None:
+            row = n // 2
+        row = int(row)
+        if not 0 <= row < n:
+            raise ValueError(f"propagate_zx: row {row} outside the valid range [0, {n}) of the output "
+                             f"{'rows' if axis == 'x' else 'columns'}")
+        bl = self._bandlimit_code()
+        x = _prop.kernel_dtype(data, "ASM_prop", field.wavelengths)
+        native = (pend is None and x.dtype == torch.complex64 and x.is_cuda
+                  and not (torch.is_grad_enabled() and x.requires_grad))
+        if axis == "x":
+            native = native and _prop.asm_slice_native(Ph)
+        else:
+            native = native and _prop.asm_slice_native(Pw) and (Ph == Pw or bl == 0)
+        max_z = _prop._lib.THZ_MAX_Z
+        if not native:
+            # full planes, at most 10 GiB of them at a time (the library's own cap on its per-chunk
+            # intermediate), sliced per chunk
+            per_z = B * C * Ho * Wo * (16 if x.dtype == torch.complex128 else 8)
+            step = int(max(1, min(max_z, (10240 * 1024 * 1024) // per_z)))
+            outs = []
+            for k in range(0, len(zs), step):
+                planes = self._run(field, zs[k:k + step])
+                outs.append(planes[..., row, :] if axis == "x" else planes[..., :, row])
+            return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+        self.shape = torch.Size([B, C, Ph, Pw])
+        wl, sp = field.wavelengths_host, field.spacing_host
+        self._zc_diagnostic(Ph, sp[0], wl, zs[0])
+        try:
+            if axis == "y":
+                x, sp, ph, pw = x.detach().transpose(-1, -2).contiguous(), (sp[1], sp[0]), pw, ph
+            else:
+                x = x.detach()
+            out = torch.empty((len(zs), B, C, Wo if axis == "x" else Ho), dtype=torch.complex64, device=x.device)
+            for k in range(0, len(zs), max_z):
+                _prop.asm_slice_apply(x, wl, sp, zs[k:k + max_z], row, ph, pw, unpad, bl, out=out[k:k + max_z])
+        except RuntimeError as err:
+            self._oom_hint()
+            raise err
+        return out

@@ -1099,6 +1099,244 @@ __global__ void __launch_bounds__(1024) THZ_ROW_ATTR asm_rows_inv_loss(const flo
   rows_inv_body<PN, true>(U, out, pw, a);
 }
 
+// ---------------------------------------------------------------------------------------------
+// z-x slice (thz_asm_slice_forward): one output row of every plane of a z-sweep
+// (experiment_extend_depth_of_focus.ipynb:229-263 keeps final_field.data[0, 0, 49, :] per z).
+// For the padded-plane row R = row + out_r0,
+//   U_z[c][R] = (1 / Ph) sum_m S_c[m] H_z(m, c) exp(+2 pi i m R / Ph),
+// S_c the column spectrum the column pass holds in registers: the z-independent phase is folded into
+// S_c once, and a plane then costs the transfer-function product and a sum -- no inverse column
+// transform, no LDS exchange, no barrier and no U store per plane.
+//   K2s cols_slice: per (bc, band column): FFT(Ph) once, x scale exp(2 pi i m R / Ph), then per z of
+//                   the chunk sum_m S'[m] H_z(m) -> V[z][bc][c]
+//   K3s rows_slice: per (z, bc): gather the band from V, IFFT(Pw), crop -> out[z][bc][w]
+// ---------------------------------------------------------------------------------------------
+// planes per cols_slice launch: the plane recurrence restarts with every launch, and its error
+// budget (D rounded once, 6e-8 per plane) is stated for 64 planes
+constexpr int SLICE_ZC = 64;
+
+// The transfer-function side is asm_cols_body's forward (ZSUM = false, a.tft = nullptr): the same
+// tasks (whole columns, then the last dispatch round's columns split into z-ranges, k2_tasks), the
+// same tf_scalars / tf_pass band bisection, sq values, recurrence_step_ok votes, plane order, step
+// factors and band zeroing, in the same fp32 operation order -- so every plane's H carries the very
+// rounding it has in asm_cols (the recurrence starts from the same planes), and the slice differs
+// from the full planes' row by the summation alone.  Kept as a copy so that asm_cols' own code and
+// registers stay as they are.
+template <int PN>
+__global__ void __launch_bounds__(1024) asm_cols_slice(const float2* __restrict__ T, float2* __restrict__ V,
+                                                      FftPlan ph, AsmArgs a, int R) {
+  extern __shared__ float2 lds[];
+  using S = Pow2Sched<PN>;
+  constexpr int TT = Geo<PN>::T;
+  static_assert(S::radix(S::NST - 1, true) == 16 && PN / 16 / TT == 1, "one radix-16 butterfly per thread");
+  int id, z_lo = 0, z_hi = a.nz;
+  if ((int)blockIdx.x < a.kfull) {
+    id = xcd_chunk(blockIdx.x, a.kfull);
+  } else {
+    const int t = blockIdx.x - a.kfull, part = t % a.kparts;
+    id = a.kfull + t / a.kparts;
+    z_lo = part * a.nz / a.kparts;
+    z_hi = (part + 1) * a.nz / a.kparts;
+  }
+  const int bc = id / a.ncols, c = id - bc * a.ncols;
+  const int nt = blockDim.x, nz = z_hi - z_lo;  // this task's planes: z_lo + [0, nz) of the chunk
+  const float2* col = T + (size_t)bc * a.ncb * CB * a.Hin + blk(c, 0, a.Hin);
+  const float lam = a.lam[bc % a.C];
+  const float Ky = kfreq(c - a.J, a.Pw, a.dy);
+  const int tid = threadIdx.x;
+  float2 sp[16];  // spectrum, element tid + r PN/16
+  const TwLds twl = load_tw_lds<PN>(lds + lds_floats2(PN), ph.tw, threadIdx.x, blockDim.x);
+  auto ld0 = [&](int, int, int idx) {
+    const int s = idx - a.in_r0;
+    return (s >= 0 && s < a.Hin) ? col[(size_t)s * CB] : make_float2(0.f, 0.f);
+  };
+  auto sv0 = [&](int, int r, int, float2 v) { sp[r] = v; };
+  fft_pow2_io<false, PN, TT, true, false, false>(lds, twl, tid, ld0, sv0);
+  // S'[m] = S[m] / (Ph Pw) exp(2 pi i ((m R) mod Ph) / Ph): the product reduced exactly in integers
+  // (m, R < 2^14), the angle in half-turns exact in fp32, so R = Ph / 2 gives exactly +-1
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int k = ((tid + r * (PN / 16)) * R) & (PN - 1);
+    float sn, cs;
+    sincospif((float)(2 * k) / (float)PN, &sn, &cs);
+    sp[r] = cmul(cscale(sp[r], a.scale), make_float2(cs, sn));
+  }
+  int* mz = reinterpret_cast<int*>(lds + lds_floats2(PN) + tw_lds_count(PN));
+  int* zok = mz + THZ_MAX_Z;
+  float* zl = reinterpret_cast<float*>(zok + THZ_MAX_Z);
+  const float kl = TWO_PI_F / lam;
+  const float kl2 = tf_mul(kl, kl);
+  const float Ky2 = tf_mul(Ky, Ky);
+  for (int zz = tid; zz < nz; zz += nt) {
+    const float zq = zval(a, a.zoff + z_lo + zz);
+    zl[zz] = zq;
+    const TfScalars s = tf_scalars(a, lam, zq);
+    int lo = -1, hi = PN / 2 + 1;
+    if (tf_pass(a.bl, a.Ph, a.dx, s, Ky, 0)) {
+      lo = 0;
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tf_pass(a.bl, a.Ph, a.dx, s, Ky, mid)) lo = mid;
+        else hi = mid;
+      }
+    }
+    mz[zz] = lo;
+    auto zv = [&](int q) { return zval(a, a.zoff + z_lo + q); };
+    const bool fwd = zz == 0 || (nz >= 2 && recurrence_step_ok(zv(0), zv(1), zv(zz - 1), zv(zz), kl));
+    const bool bwd = zz == nz - 1 || (nz >= 2 && recurrence_step_ok(zv(nz - 1), zv(nz - 2), zv(zz + 1), zv(zz), kl));
+    const bool inward = zz == 0 && fabsf(zv(nz - 1)) < fabsf(zv(0));
+    zok[zz] = (fwd ? 1 : 0) | (bwd ? 2 : 0) | (inward ? 4 : 0);
+  }
+  float sq[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float Kx = kfreq(freq_index(tid + r * (PN / 16), PN), PN, a.dx);
+    sq[r] = sqrtf(fmaxf(tf_sub(kl2, tf_add(tf_mul(Kx, Kx), Ky2)), 0.0f));
+  }
+  __syncthreads();  // mz, zok, zl visible; every wave is done with the transform's LDS image
+  bool rec = false, rev = false;
+  const int lane = threadIdx.x & 63;
+  if (a.zrec && nz >= 3) {
+    bool okf = true, okr = true, wide = false;
+    for (int q0 = 0; q0 < nz; q0 += 64) {
+      const int q = q0 + lane;
+      bool pf = true, pr = true, pw = false;
+      if (q < nz) {
+        const int m = mz[q], mp = q > 0 ? mz[q - 1] : m, zk = zok[q];
+        pf = (zk & 1) && m <= mp;
+        pr = (zk & 2) && m >= mp;
+        pw = m >= PN / 4;
+      }
+      okf = okf && __ballot(!pf) == 0;
+      okr = okr && __ballot(!pr) == 0;
+      wide = wide || __ballot(pw) != 0;
+    }
+    rec = (okf || okr) && !wide;
+    const int zk0 = __builtin_amdgcn_readfirstlane(zok[0]);
+    rev = rec && okr && (!okf || (zk0 & 4));
+  }
+  // each wave's partial sum of plane zz in slot [zz][wave] of the (now free) transform image;
+  // the planes are finished after the loop in a fixed order (no barrier inside the z loop)
+  float2* part = lds;
+  const int wave = threadIdx.x >> 6, nw = nt >> 6;
+  float2 dstep[8];  // the step factors D of the kept values r < 4 (slots 0..3) and r >= 12 (4..7)
+  float dz = 0.f, zprev = 0.f;
+  int Mprev = -2;
+  const int zfirst = rev ? nz - 1 : 0, zstep = rev ? -1 : 1;
+  if (rec) {
+    const float z0 = zl[zfirst];
+    dz = zl[zfirst + zstep] - z0;
+    zprev = z0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (r >= 4 && r < 12) continue;
+      float sn, cs;
+      sincos_hw(tf_mul(z0, sq[r]), &sn, &cs);
+      sp[r] = cmul(sp[r], make_float2(cs, sn));
+      dstep[r < 4 ? r : r - 8] = cis_dd((double)dz * (double)sq[r]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  for (int it = 0; it < nz; ++it) {
+    const int zz = zfirst + it * zstep;
+    const float z = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(zl[zz])));
+    const int M = mz[zz];
+    const int Ms = __builtin_amdgcn_readfirstlane(M);
+    float2 acc = make_float2(0.f, 0.f);
+    if (rec) {
+      if (it > 0) {
+        const float eps = tf_sub(tf_sub(z, zprev), dz);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if (r >= 4 && r < 12) continue;
+          sp[r] = cmul(sp[r], dstep[r < 4 ? r : r - 8]);
+        }
+        if (__builtin_amdgcn_readfirstlane(__float_as_int(eps)) != 0) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            if (r >= 4 && r < 12) continue;
+            const float2 g = sp[r];
+            const float th = eps * sq[r];
+            sp[r] = make_float2(fmaf(-th, g.y, g.x), fmaf(th, g.x, g.y));
+          }
+        }
+      }
+      zprev = z;
+      if (Ms != Mprev) {  // the band's edge: elements that leave the band are zeroed for good
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if (r >= 4 && r < 12) continue;
+          const bool keep = r < 4 ? tid <= Ms - r * (PN / 16) : tid >= PN - r * (PN / 16) - Ms;
+          if (!keep) sp[r] = make_float2(0.f, 0.f);
+        }
+      }
+      Mprev = Ms;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (r >= 4 && r < 12) continue;
+        acc = cadd(acc, sp[r]);
+      }
+    } else {
+      const bool mid0 = Ms < PN / 4;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (r >= 4 && r < 12 && mid0) continue;
+        const int mx = freq_index(tid + r * (PN / 16), PN);
+        if (mx > M || -mx > M) continue;
+        float sn, cs;
+        sincos_hw(tf_mul(z, sq[r]), &sn, &cs);
+        acc = cadd(acc, cmul(sp[r], make_float2(cs, sn)));
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      acc.x += __shfl_xor(acc.x, o);
+      acc.y += __shfl_xor(acc.y, o);
+    }
+    if (lane == 0) part[zz * nw + wave] = acc;
+  }
+  __syncthreads();
+  for (int zz = tid; zz < nz; zz += nt) {
+    float2 v = part[zz * nw];
+    for (int w = 1; w < nw; ++w) v = cadd(v, part[zz * nw + w]);
+    V[((size_t)(z_lo + zz) * a.BC + bc) * a.ncols + c] = v;
+  }
+}
+
+// PN > 0: the compile-time power-of-two row transform of asm_rows_inv with a plain loader (V holds
+// one value per band column); PN == 0: the runtime plan, data staged through LDS.
+template <int PN>
+__global__ void __launch_bounds__(1024) asm_rows_slice(const float2* __restrict__ V, float2* __restrict__ out,
+                                                      FftPlan pw, AsmArgs a) {
+  extern __shared__ float2 lds[];
+  const int plane = blockIdx.x;  // zz * BC + bc
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const float2* src = V + (size_t)plane * a.ncols;
+  float2* dst = out + ((size_t)a.zoff * a.BC + plane) * a.Wout;
+  if constexpr (PN > 0) {
+    constexpr int TT = Geo<PN>::T;
+    const auto twf = tw_fetch<PN, TT>(pw.tw, tid);
+    const TwLds twl = tw_lds_at<PN>(tw_slot<PN>(lds));
+    auto tw_hook = [&]() { tw_store<PN, TT>(tw_slot<PN>(lds), twf, tid); };
+    auto ld = [&](int, int, int j) {
+      const int c = band_col(j, PN, a.J, a.ncols);
+      return c >= 0 ? src[c] : make_float2(0.f, 0.f);
+    };
+    auto sv = [&](int, int, int j, float2 v) {
+      const int w = j - a.out_c0;
+      if ((unsigned)w < (unsigned)a.Wout) dst[w] = v;
+    };
+    fft_pow2_run<true, PN, TT, FFT_ROWS>(lds, twl, tid, ld, sv, tw_hook);
+  } else {
+    for (int j = tid; j < a.Pw; j += nt) {
+      const int c = band_col(j, a.Pw, a.J, a.ncols);
+      lds[padx(j)] = c >= 0 ? src[c] : make_float2(0.f, 0.f);
+    }
+    __syncthreads();
+    fft_lds<true>(lds, pw, tid, nt);
+    for (int w = tid; w < a.Wout; w += nt) dst[w] = lds[padx(a.out_c0 + w)];
+  }
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // RSC (Props/RSC_Prop.py:129-215): transfer function = FFT2 of the spatial RS kernel on the
@@ -1312,6 +1550,12 @@ static void add_kernels(std::vector<const void*>& ks) {
   ks.push_back((const void*)rsc_k_cols<PN>);
 }
 
+template <int PN>
+static void add_slice_kernels(std::vector<const void*>& ks) {
+  ks.push_back((const void*)asm_cols_slice<PN>);
+  ks.push_back((const void*)asm_rows_slice<PN>);
+}
+
 // Workgroups above 64 KiB of dynamic LDS must opt in once per kernel.
 static int ensure_lds_attr() {
   static std::once_flag once;
@@ -1325,6 +1569,12 @@ static int ensure_lds_attr() {
     add_kernels<4096>(ks);
     add_kernels<8192>(ks);
     add_kernels<16384>(ks);
+    add_slice_kernels<1024>(ks);
+    add_slice_kernels<2048>(ks);
+    add_slice_kernels<4096>(ks);
+    add_slice_kernels<8192>(ks);
+    add_slice_kernels<16384>(ks);
+    ks.push_back((const void*)asm_rows_slice<0>);
     for (const void* k : ks) {
       hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
       if (e != hipSuccess) err = e;
@@ -1574,9 +1824,126 @@ static int run_pipeline(AsmArgs a, const AsmGeom& g, int Z, const void* in, void
   return THZ_OK;
 }
 
+// the z-x slice kernels: the column pass exists for the compile-time power-of-two heights only
+#define THZ_SLICE_COLS(n, ...)                                                                     \
+  switch (n) {                                                                                     \
+    case 1024: hipLaunchKernelGGL(asm_cols_slice<1024>, __VA_ARGS__); break;                       \
+    case 2048: hipLaunchKernelGGL(asm_cols_slice<2048>, __VA_ARGS__); break;                       \
+    case 4096: hipLaunchKernelGGL(asm_cols_slice<4096>, __VA_ARGS__); break;                       \
+    case 8192: hipLaunchKernelGGL(asm_cols_slice<8192>, __VA_ARGS__); break;                       \
+    default: hipLaunchKernelGGL(asm_cols_slice<16384>, __VA_ARGS__); break;                        \
+  }
+
+// planes per cols_slice launch: the full path's z-chunk (so the recurrence starts where it does
+// there), at most SLICE_ZC
+static int slice_zc(const AsmGeom& g) { return std::min(g.zc, SLICE_ZC); }
+static size_t slice_v_bytes(const AsmGeom& g) {
+  return align256((size_t)slice_zc(g) * g.BC * g.ncols * sizeof(float2));  // V [zc][BC][ncols]
+}
+static size_t slice_ws_bytes(const AsmGeom& g) { return t_bytes(g) + slice_v_bytes(g); }
+
+// K1 once, then (cols_slice, rows_slice) per z-chunk: row R of the padded plane
+static int run_slice(AsmArgs a, const AsmGeom& g, int Z, int R, const void* in, void* out, float2* T, float2* V,
+                     hipStream_t s, FftPlan pw, FftPlan ph) {
+  int e;
+  if ((e = ensure_lds_attr())) return e;
+  a.tab_blocks = 0;
+  a.zoff = 0;
+  const int zc = slice_zc(g), th = threads_for(g.Ph);
+  a.nz = std::min(zc, Z);
+  {
+    KernelTimer kt("asm_rows_fwd", s);
+    THZ_ROWS_SWITCH(g.Pw, asm_rows_fwd, dim3(g.BC * g.Hin), fft_lds_bytes_io(g.Pw), s, (const float2*)in, T, pw, a);
+    THZ_LAUNCH_CHECK();
+    kt.stop();
+  }
+  const size_t lds2 = fft_lds_bytes(g.Ph) + 12 * THZ_MAX_Z;  // mz, zok and the z values, as asm_cols
+  a.zrec = !plane_recurrence_disabled();
+  for (int z0 = 0; z0 < Z; z0 += zc) {
+    a.zoff = z0;
+    a.nz = std::min(zc, Z - z0);
+    {
+      KernelTimer kt("asm_cols_slice", s);
+      const int ntask = k2_tasks(g, &a, th, lds2);  // asm_cols' own task split
+      THZ_SLICE_COLS(g.Ph, dim3(ntask), dim3(th), lds2, s, (const float2*)T, V, ph, a, R);
+      THZ_LAUNCH_CHECK();
+      kt.stop();
+    }
+    {
+      KernelTimer kt("asm_rows_slice", s);
+      THZ_POW2_SWITCH(g.Pw, asm_rows_slice, dim3(a.nz * g.BC), dim3(threads_for(g.Pw)), fft_lds_bytes_io(g.Pw), s,
+                      (const float2*)V, (float2*)out, pw, a);
+      THZ_LAUNCH_CHECK();
+      kt.stop();
+    }
+  }
+  return THZ_OK;
+}
+
+// what thz_asm_slice_* accept, checked on the host before any device call
+static int validate_slice(const thz_asm_desc* d) {
+  int e = validate(d);
+  if (e) return e;
+  if (d->adjoint) return fail(THZ_E_UNSUPPORTED, "z-x slice: forward only (no adjoint)");
+  if (d->z_dev) return fail(THZ_E_UNSUPPORTED, "z-x slice: host plane distances only (z_dev is not read)");
+  if (!d->z) return fail(THZ_E_ARG, "null z");
+  if (d->window_mask) return fail(THZ_E_UNSUPPORTED, "z-x slice: no window mask (apply the aperture separately)");
+  const int Ph = d->H + 2 * d->pad_h;
+  if (!pow2_kind(Ph))
+    return fail(THZ_E_UNSUPPORTED, "z-x slice: padded height %d is not one of 1024, 2048, 4096, 8192, 16384 "
+                                   "(slice thz_asm_forward's planes instead)", Ph);
+  return THZ_OK;
+}
+
 }  // namespace thz
 
 using namespace thz;
+
+extern "C" int thz_asm_slice_workspace_size(const thz_asm_desc* d, size_t* bytes) {
+  int e = validate_slice(d);
+  if (e) return e;
+  if (!bytes) return fail(THZ_E_ARG, "null bytes");
+  AsmGeom g;
+  geometry(d, &g);
+  *bytes = slice_ws_bytes(g);
+  return THZ_OK;
+}
+
+extern "C" int thz_asm_slice_forward(const thz_asm_desc* d, int row, const void* in, void* out, void* workspace,
+                                     size_t workspace_bytes, thz_stream_t stream) {
+  int e = validate_slice(d);
+  if (e) return e;
+  AsmGeom g;
+  geometry(d, &g);
+  if (row < 0 || row >= g.Hout) return fail(THZ_E_ARG, "z-x slice: row %d outside [0, %d)", row, g.Hout);
+  if (!in || !out) return fail(THZ_E_ARG, "null data pointer");
+  const size_t need = slice_ws_bytes(g);
+  if (!workspace || workspace_bytes < need)
+    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  FftPlan pw, ph;
+  if ((e = get_plan(g.Pw, &pw))) return e;
+  if ((e = get_plan(g.Ph, &ph))) return e;
+  AsmArgs a{};
+  a.BC = g.BC;
+  a.C = d->C;
+  a.Ph = g.Ph;
+  a.Pw = g.Pw;
+  a.in_r0 = d->pad_h; a.in_c0 = d->pad_w; a.Hin = d->H; a.Win = d->W;
+  a.out_r0 = d->unpad ? d->pad_h : 0; a.out_c0 = d->unpad ? d->pad_w : 0; a.Hout = g.Hout; a.Wout = g.Wout;
+  a.ncols = g.ncols;
+  a.ncb = g.ncb;
+  a.ncbu = g.ncbu;
+  a.J = g.J;
+  a.bl = d->bandlimit;
+  a.dx = d->dx;
+  a.dy = d->dy;
+  a.scale = (float)(1.0 / ((double)g.Ph * (double)g.Pw));
+  for (int c = 0; c < d->C; ++c) a.lam[c] = d->wavelengths[c];
+  for (int zi = 0; zi < d->Z; ++zi) a.zv[zi] = d->z[zi];
+  float2* T = (float2*)workspace;
+  float2* V = (float2*)((char*)workspace + t_bytes(g));
+  return run_slice(a, g, d->Z, row + a.out_r0, in, out, T, V, (hipStream_t)stream, pw, ph);
+}
 
 extern "C" int thz_asm_band(const thz_asm_desc* d, int* ncols, int* z_chunk) {
   int e = validate(d);

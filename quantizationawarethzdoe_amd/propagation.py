@@ -124,6 +124,41 @@ def asm_apply(data, wavelengths, spacing, zs, pad_h, pad_w, unpad, bandlimit, ad
     return out
 
 
+ASM_SLICE_HEIGHTS = (1024, 2048, 4096, 8192, 16384)  # padded heights thz_asm_slice_forward serves
+
+
+def asm_slice_native(padded_height):
+    """True when the z-x slice kernels serve this padded height (the compile-time power-of-two
+    column passes); other heights slice the full planes (ASM_prop.propagate_zx)."""
+    return int(padded_height) in ASM_SLICE_HEIGHTS
+
+
+def asm_slice_apply(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, out=None):
+    """Raw launch of the z-x slice (thz_asm_slice_forward): data [B,C,H,W] complex64 -> [Z,B,C,Wo],
+    output row ``row`` of every plane of ``zs`` (at most THZ_MAX_Z), equal to
+    asm_apply(...)[:, :, :, row, :] without forming the planes.  Forward only, not differentiable."""
+    _require_device(data, "ASM slice")
+    if data.dtype != torch.complex64:
+        raise TypeError(f"ASM slice kernels compute in complex64; got {data.dtype}")
+    L = _lib.lib()
+    data = data.contiguous()
+    B, C, H, W = data.shape
+    Wo = W if unpad else W + 2 * pad_w
+    d = _asm_desc(B, C, H, W, pad_h, pad_w, unpad, bandlimit, wavelengths, spacing, zs, False)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.thz_asm_slice_workspace_size(ctypes.byref(d), ctypes.byref(nbytes)))
+    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=data.device)
+    if out is None:
+        out = torch.empty((len(zs), B, C, Wo), dtype=torch.complex64, device=data.device)
+    elif tuple(out.shape) != (len(zs), B, C, Wo) or out.dtype != torch.complex64 or not out.is_contiguous():
+        raise ValueError(f"ASM slice: out must be a contiguous complex64 {(len(zs), B, C, Wo)} tensor")
+    with torch.cuda.device(data.device):
+        _lib.check(L.thz_asm_slice_forward(ctypes.byref(d), int(row), ctypes.c_void_p(data.data_ptr()),
+                                           ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                           ctypes.c_size_t(ws.numel()), _stream_handle()))
+    return out
+
+
 def _asm64_apply(data, wavelengths, spacing, zs, pad_h, pad_w, unpad, bandlimit, adjoint=False, out=None):
     """complex128 ASM (thz_asm64_forward): the same shapes as asm_apply; the fp64 adjoint runs one
     launch per plane and sums them."""
