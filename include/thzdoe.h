@@ -53,7 +53,9 @@ typedef void* thz_stream_t; /* hipStream_t */
  * rng / rng_stream to thz_doe_desc and thz_quant_desc; 4 added thz_asm_transfer_function and
  * thz_rs_kernel, which the bindings require; 5 appended thz_asm_desc.window_mask, 6 thz_asm_desc.z_dev,
  * 7 added thz_doe_quant_backward and thz_radial_quant_backward, 8 thz_step_fetch and
- * thz_adam_step, 9 thz_asm_slice_workspace_size and thz_asm_slice_forward):
+ * thz_adam_step, 9 thz_asm_slice_workspace_size and thz_asm_slice_forward;
+ * thz_asm_slice_adjoint_workspace_size and thz_asm_slice_adjoint (library 0.6.0) changed no struct and
+ * are purely additive, so the version stays 9 -- a caller detects them by symbol):
  * a caller compares thz_abi_version()
  * with the THZ_ABI_VERSION it was compiled against before its first call, since a shorter
  * struct from an older header would make the library read past it.  Descriptors are plain C
@@ -126,7 +128,7 @@ int thz_asm_forward(const thz_asm_desc* d, const void* in, void* out, void* work
  * The row pass runs as in thz_asm_forward; the column pass folds exp(2 pi i m R / Ph) of the padded
  * row R into the column spectrum once and then sums spectrum x H_z per plane (no inverse column
  * transform, no per-plane intermediate of height Ho); one Pw-point inverse row transform per
- * (z, b, c).  Forward only, host z[] only, no window mask: adjoint != 0, z_dev != NULL and
+ * (z, b, c).  Forward only (its adjoint is thz_asm_slice_adjoint below), host z[] only, no window mask: adjoint != 0, z_dev != NULL and
  * window_mask != NULL return THZ_E_UNSUPPORTED, as does a padded height H + 2 pad_h other than
  * 1024, 2048, 4096, 8192 or 16384 (slice thz_asm_forward's planes there); a bad row or a null
  * pointer THZ_E_ARG; a short workspace THZ_E_WORKSPACE -- all before any device call.
@@ -136,6 +138,24 @@ int thz_asm_forward(const thz_asm_desc* d, const void* in, void* out, void* work
 int thz_asm_slice_workspace_size(const thz_asm_desc* d, size_t* bytes);
 int thz_asm_slice_forward(const thz_asm_desc* d, int row, const void* in, void* out /* [Z,B,C,Wo] */,
                           void* workspace, size_t workspace_bytes, thz_stream_t stream);
+/*
+ * Adjoint of the z-x slice (the autograd backward of thz_asm_slice_forward; library 0.6.0):
+ *   grad_out [Z, B, C, Wo] -> grad_in [B, C, H, W] = sum over z of A_{z,row}^H grad_out[z]
+ * d is the forward's descriptor with adjoint == 1 (anything else: THZ_E_ARG); row as in the forward.
+ * One forward Pw-point row transform per (z, b, c) (asm_rows_fwd on one-row planes), one column pass
+ * that sums conj(H_z) x the rows' spectra over all Z planes in registers (the forward's band, plane
+ * recurrence and step factors, conjugated; a fresh sincos anchor at least every 64 planes) and
+ * inverts once per column, and the adjoint's usual inverse row pass (asm_rows_inv).  Two calls with
+ * the same inputs are bit-identical (fixed summation order, no atomics).  Validation as the
+ * forward's, before any device call: z_dev, window_mask and a padded height outside the five powers
+ * of two THZ_E_UNSUPPORTED; a bad row or a null pointer THZ_E_ARG; a short workspace THZ_E_WORKSPACE.
+ * Workspace: the gradient spectrum of ONE plane [BC][ncols][H] and the rows' spectra
+ * Gv [Z][BC][ncols rounded up to 16], both complex64 -- nothing of a plane's size per z.
+ */
+int thz_asm_slice_adjoint_workspace_size(const thz_asm_desc* d, size_t* bytes);
+int thz_asm_slice_adjoint(const thz_asm_desc* d, int row, const void* grad_out /* [Z,B,C,Wo] */,
+                          void* grad_in /* [B,C,H,W] */, void* workspace, size_t workspace_bytes,
+                          thz_stream_t stream);
 /* Plan facts for diagnostics / bench byte counts: number of spectral columns the kernels
  * keep (|m_y| <= J; ncols = 2J+1, or Pw when nothing is cut) and z-planes per column pass. */
 int thz_asm_band(const thz_asm_desc* d, int* ncols, int* z_chunk);
@@ -511,7 +531,8 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * enabled every kernel launch is bracketed by two events on its own stream;
  * thz_timing_read() synchronises on the pending events and returns the summed
  * duration and launch count for one kernel name ("asm_rows_fwd", "asm_cols", "asm_rows_inv"; the
- * z-x slice: "asm_rows_fwd", "asm_cols_slice", "asm_rows_slice"; ...).
+ * z-x slice: "asm_rows_fwd", "asm_cols_slice", "asm_rows_slice"; its adjoint: "asm_rows_fwd",
+ * "asm_cols_slice_adj", "asm_rows_inv"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

@@ -309,7 +309,7 @@ class ASM_prop(nn.Module):
             outs.append(self._run(field, zs[k:k + _prop._lib.THZ_MAX_Z]))
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
-    def propagate_zx(self, field: ElectricField, z_list, row=None, axis="x") -> torch.Tensor:
+    def propagate_zx(self, field: ElectricField, z_list, row=None, axis="x", grad="planes") -> torch.Tensor:
         """Additive API: one output row of every plane of ``z_list`` -> [Z, B, C, Wo], equal to
         ``propagate_planes(field, z_list)[..., row, :]`` -- the z-x map of the extend-DOF notebook
         (experiment_extend_depth_of_focus.ipynb:229-263 keeps ``final_field.data[0, 0, 49, :]`` of
@@ -322,11 +322,25 @@ class ASM_prop(nn.Module):
         ``axis="y"`` runs them on the transposed field with dx / dy and the paddings exchanged (one
         transpose of the input); the reference's band limits take both frequency steps from the
         padded height, so that holds for a square padded plane or with no band limit.  Every other
-        input -- another padded height, a complex128 field, a pending fused DOE modulation, an input
-        that requires grad (the slice kernels have no adjoint) -- propagates the full planes in
-        z-chunks whose temporary stays under 10 GiB and slices each chunk, differentiably."""
+        input -- another padded height, a complex128 field, ``axis="y"`` on a non-square band-limited
+        plane -- propagates the full planes in z-chunks whose temporary stays under 10 GiB and
+        slices each chunk, differentiably.
+
+        ``grad`` chooses what serves a differentiated call.  ``"planes"`` (the default): an input
+        that requires grad, and a field that carries a pending fused DOE modulation, also take the
+        full-plane path, forward and backward.  ``"slice"``: the slice kernels serve them as well,
+        whether or not the input requires grad, and the backward is their own adjoint
+        (thz_asm_slice_adjoint: the planes' cotangent rows are summed in one column pass, nothing of
+        a plane's size per z in either direction).  A pending DOE modulation is then formed by the
+        differentiable modulate kernel (its output kept for later readers of the field) and sliced
+        natively, so the gradient reaches the field, the height map and the quantiser weight;
+        ``axis="y"`` transposes outside the slice (torch differentiates the transpose).  Inputs the
+        slice kernels do not serve fall back to the full planes as above.  Any other value is a
+        ValueError."""
         if axis not in ("x", "y"):
             raise ValueError(f"propagate_zx: axis must be 'x' or 'y', got {axis!r}")
+        if grad not in ("planes", "slice"):
+            raise ValueError(f"propagate_zx: grad must be 'planes' or 'slice', got {grad!r}")
         zs = _z_host(z_list)
         pend = field._take_pending()
         data = pend.field if pend is not None else field.data
@@ -344,8 +358,9 @@ class ASM_prop(nn.Module):
                              f"{'rows' if axis == 'x' else 'columns'}")
         bl = self._bandlimit_code()
         x = _prop.kernel_dtype(data, "ASM_prop", field.wavelengths)
-        native = (pend is None and x.dtype == torch.complex64 and x.is_cuda
-                  and not (torch.is_grad_enabled() and x.requires_grad))
+        native = x.dtype == torch.complex64 and x.is_cuda
+        if grad == "planes":
+            native = native and pend is None and not (torch.is_grad_enabled() and x.requires_grad)
         if axis == "x":
             native = native and _prop.asm_slice_native(Ph)
         else:
@@ -365,6 +380,12 @@ class ASM_prop(nn.Module):
         wl, sp = field.wavelengths_host, field.spacing_host
         self._zc_diagnostic(Ph, sp[0], wl, zs[0])
         try:
+            if grad == "slice":
+                if pend is not None:  # the differentiable modulate kernel; the slice reads its output
+                    x = _prop.kernel_dtype(pend.run(), "ASM_prop", field.wavelengths)
+                if axis == "y":
+                    x, sp, ph, pw = x.transpose(-1, -2), (sp[1], sp[0]), pw, ph
+                return _prop.asm_propagate_zx(x, wl, sp, zs, row, ph, pw, unpad=unpad, bandlimit=bl)
             if axis == "y":
                 x, sp, ph, pw = x.detach().transpose(-1, -2).contiguous(), (sp[1], sp[0]), pw, ph
             else:

@@ -30,6 +30,7 @@ EXPORTED = [
     "thz_asm_workspace_size", "thz_asm_forward", "thz_asm_band", "thz_asm_forward_modulated",
     "thz_asm_forward_loss", "thz_asm_adjoint_loss", "thz_asm_transfer_function", "thz_rs_kernel",
     "thz_asm_slice_workspace_size", "thz_asm_slice_forward",
+    "thz_asm_slice_adjoint_workspace_size", "thz_asm_slice_adjoint",
     "thz_czt_workspace_size", "thz_czt_forward",
     "thz_rsc_workspace_size", "thz_rsc_forward",
     "thz_doe_modulate_forward", "thz_doe_modulate_backward", "thz_quant_forward", "thz_quant_backward",
@@ -202,6 +203,9 @@ def _declare(lib):
     lib.thz_asm_forward.argtypes = [ctypes.POINTER(AsmDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.thz_asm_slice_workspace_size.argtypes = [ctypes.POINTER(AsmDesc), ctypes.POINTER(c_size_t)]
     lib.thz_asm_slice_forward.argtypes = [ctypes.POINTER(AsmDesc), c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]
+    lib.thz_asm_slice_adjoint_workspace_size.argtypes = [ctypes.POINTER(AsmDesc), ctypes.POINTER(c_size_t)]
+    lib.thz_asm_slice_adjoint.argtypes = [ctypes.POINTER(AsmDesc), c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p]
     lib.thz_asm_band.argtypes = [ctypes.POINTER(AsmDesc), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     lib.thz_asm_forward_modulated.argtypes = [ctypes.POINTER(AsmDesc), ctypes.POINTER(DoeDesc), c_void_p, c_void_p,

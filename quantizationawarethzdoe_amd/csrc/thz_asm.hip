@@ -1337,6 +1337,190 @@ __global__ void __launch_bounds__(1024) asm_rows_slice(const float2* __restrict_
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Adjoint of the z-x slice (thz_asm_slice_adjoint): g [Z][BC][Wo] -> gx [BC][H][W] = A_R^H g.
+//   K1  rows_fwd      : the forward Pw-point transform of each cotangent row, band columns kept
+//                       (asm_rows_fwd on a one-row geometry) -> Gv[z][bc][c]
+//   K2a cols_slice_adj: per (bc, band column): Q[m] = conj(scale exp(2 pi i m R / Ph))
+//                       sum_z conj(H_z(m)) Gv[z], one unnormalised inverse Ph-point transform,
+//                       rows in_r0 .. in_r0 + H - 1 of it -> U (one plane)
+//   K3  rows_inv      : asm_rows_inv on U -> gx
+// `a` is the adjoint's argument block (in_* the forward's output window, out_* its input window).
+// ---------------------------------------------------------------------------------------------
+// One whole-column task per (bc, c); the planes are summed in segments of SLICE_ZC planes, each
+// with the forward's own votes, plane order, anchor and step factors (the transfer-function side is
+// asm_cols_slice's, conjugated), so the recurrence never runs more than SLICE_ZC steps from a
+// sincos anchor.  Under the recurrence H_j = A prod_{k <= j} s_k (A the anchor, s_k = D (1 + i eps_k sq))
+// and the segment's sum is a polynomial in the conjugate steps, run as Horner steps from the
+// segment's far plane inward: acc = (acc + Gv_j) conj(s_j), and conj(A) once at the end.  The band
+// only narrows in the order the planes are run, so an element enters the sum at the last plane
+// that still holds it.  Every sum runs in a fixed order in registers: two calls are bit-identical.
+template <int PN>
+__global__ void __launch_bounds__(1024) asm_cols_slice_adj(const float2* __restrict__ Gv, float2* __restrict__ U,
+                                                          FftPlan ph, AsmArgs a, int R) {
+  extern __shared__ float2 lds[];
+  using S = Pow2Sched<PN>;
+  constexpr int TT = Geo<PN>::T;
+  static_assert(S::radix(S::NST - 1, true) == 16 && PN / 16 / TT == 1, "one radix-16 butterfly per thread");
+  static_assert(lds_floats2(PN) >= THZ_MAX_Z, "the column's Gv values fit the transform image");
+  const int id = xcd_chunk(blockIdx.x, gridDim.x);
+  const int bc = id / a.ncols, c = id - bc * a.ncols;
+  const int nt = blockDim.x, Z = a.nz;
+  const float lam = a.lam[bc % a.C];
+  const float Ky = kfreq(c - a.J, a.Pw, a.dy);
+  const int tid = threadIdx.x;
+  const TwLds twl = load_tw_lds<PN>(lds + lds_floats2(PN), ph.tw, threadIdx.x, blockDim.x);
+  // the column's Gv values in the transform image (free until the inverse transform): read
+  // wave-uniform in the z loops
+  float2* gl = lds;
+  int* mz = reinterpret_cast<int*>(lds + lds_floats2(PN) + tw_lds_count(PN));
+  int* zok = mz + THZ_MAX_Z;
+  float* zl = reinterpret_cast<float*>(zok + THZ_MAX_Z);
+  const float kl = TWO_PI_F / lam;
+  const float kl2 = tf_mul(kl, kl);
+  const float Ky2 = tf_mul(Ky, Ky);
+  for (int zz = tid; zz < Z; zz += nt) {
+    gl[zz] = Gv[((size_t)zz * a.BC + bc) * a.ncb * CB + c];
+    const float zq = zval(a, zz);
+    zl[zz] = zq;
+    const TfScalars s = tf_scalars(a, lam, zq);
+    int lo = -1, hi = PN / 2 + 1;
+    if (tf_pass(a.bl, a.Ph, a.dx, s, Ky, 0)) {
+      lo = 0;
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tf_pass(a.bl, a.Ph, a.dx, s, Ky, mid)) lo = mid;
+        else hi = mid;
+      }
+    }
+    mz[zz] = lo;
+    // the votes of the plane's own segment [s0, s0 + nzs), as asm_cols_slice takes them per launch
+    const int s0 = zz / SLICE_ZC * SLICE_ZC, nzs = min(SLICE_ZC, Z - s0), q = zz - s0;
+    auto zv = [&](int k) { return zval(a, s0 + k); };
+    const bool fwd = q == 0 || (nzs >= 2 && recurrence_step_ok(zv(0), zv(1), zv(q - 1), zv(q), kl));
+    const bool bwd = q == nzs - 1 || (nzs >= 2 && recurrence_step_ok(zv(nzs - 1), zv(nzs - 2), zv(q + 1), zv(q), kl));
+    const bool inward = q == 0 && fabsf(zv(nzs - 1)) < fabsf(zv(0));
+    zok[zz] = (fwd ? 1 : 0) | (bwd ? 2 : 0) | (inward ? 4 : 0);
+  }
+  float sq[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float Kx = kfreq(freq_index(tid + r * (PN / 16), PN), PN, a.dx);
+    sq[r] = sqrtf(fmaxf(tf_sub(kl2, tf_add(tf_mul(Kx, Kx), Ky2)), 0.0f));
+  }
+  __syncthreads();  // gl, mz, zok, zl visible
+  float2 qs[16];    // Q, element tid + r PN/16
+#pragma unroll
+  for (int r = 0; r < 16; ++r) qs[r] = make_float2(0.f, 0.f);
+  const int lane = threadIdx.x & 63;
+  for (int s0 = 0; s0 < Z; s0 += SLICE_ZC) {
+    const int nzs = min(SLICE_ZC, Z - s0);
+    bool rec = false, rev = false;
+    if (a.zrec && nzs >= 3) {
+      // one plane per lane (nzs <= 64), every wave voting on its own copy
+      bool pf = true, pr = true, pw = false;
+      if (lane < nzs) {
+        const int m = mz[s0 + lane], mp = lane > 0 ? mz[s0 + lane - 1] : m, zk = zok[s0 + lane];
+        pf = (zk & 1) && m <= mp;
+        pr = (zk & 2) && m >= mp;
+        pw = m >= PN / 4;
+      }
+      const bool okf = __ballot(!pf) == 0, okr = __ballot(!pr) == 0, wide = __ballot(pw) != 0;
+      rec = (okf || okr) && !wide;
+      const int zk0 = __builtin_amdgcn_readfirstlane(zok[s0]);
+      rev = rec && okr && (!okf || (zk0 & 4));
+    }
+    if (rec) {
+      const int zfirst = rev ? s0 + nzs - 1 : s0, zstep = rev ? -1 : 1;
+      const float z0 = zl[zfirst];
+      const float dz = zl[zfirst + zstep] - z0;
+      float2 acc[8], dstep[8];  // the kept values r < 4 (slots 0..3) and r >= 12 (4..7)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (r >= 4 && r < 12) continue;
+        const float2 d = cis_dd((double)dz * (double)sq[r]);
+        dstep[r < 4 ? r : r - 8] = make_float2(d.x, -d.y);
+        acc[r < 4 ? r : r - 8] = make_float2(0.f, 0.f);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      for (int it = nzs - 1; it >= 0; --it) {
+        const int zz = zfirst + it * zstep;
+        const int Ms = __builtin_amdgcn_readfirstlane(mz[zz]);
+        const float gx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(gl[zz].x)));
+        const float gy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(gl[zz].y)));
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if (r >= 4 && r < 12) continue;
+          // element tid + r PN/16: m_x = tid + r PN/16 (r < 4), tid + r PN/16 - PN (r >= 12)
+          const bool keep = r < 4 ? tid <= Ms - r * (PN / 16) : tid >= PN - r * (PN / 16) - Ms;
+          float2& v = acc[r < 4 ? r : r - 8];
+          v.x += keep ? gx : 0.f;
+          v.y += keep ? gy : 0.f;
+        }
+        if (it > 0) {
+          const float z = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(zl[zz])));
+          const float zprev = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(zl[zz - zstep])));
+          const float eps = tf_sub(tf_sub(z, zprev), dz);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) acc[k] = cmul(acc[k], dstep[k]);
+          if (__builtin_amdgcn_readfirstlane(__float_as_int(eps)) != 0) {  // conj(1 + i eps sq)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              if (r >= 4 && r < 12) continue;
+              const float2 g = acc[r < 4 ? r : r - 8];
+              const float th = eps * sq[r];
+              acc[r < 4 ? r : r - 8] = make_float2(fmaf(th, g.y, g.x), fmaf(-th, g.x, g.y));
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (r >= 4 && r < 12) continue;
+        float sn, cs;
+        sincos_hw(tf_mul(z0, sq[r]), &sn, &cs);
+        qs[r] = cadd(qs[r], cmul(acc[r < 4 ? r : r - 8], make_float2(cs, -sn)));
+      }
+    } else {
+      for (int zz = s0; zz < s0 + nzs; ++zz) {
+        const float z = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(zl[zz])));
+        const int M = mz[zz];
+        const int Ms = __builtin_amdgcn_readfirstlane(M);
+        const float gx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(gl[zz].x)));
+        const float gy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(gl[zz].y)));
+        const bool mid0 = Ms < PN / 4;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if (r >= 4 && r < 12 && mid0) continue;
+          const int mx = freq_index(tid + r * (PN / 16), PN);
+          if (mx > M || -mx > M) continue;
+          float sn, cs;
+          sincos_hw(tf_mul(z, sq[r]), &sn, &cs);
+          qs[r] = cadd(qs[r], cmul(make_float2(gx, gy), make_float2(cs, -sn)));
+        }
+      }
+    }
+  }
+  // Q[m] = conj(exp(2 pi i ((m R) mod Ph) / Ph) / (Ph Pw)) x the sum: the angle as in asm_cols_slice
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int k = ((tid + r * (PN / 16)) * R) & (PN - 1);
+    float sn, cs;
+    sincospif((float)(2 * k) / (float)PN, &sn, &cs);
+    qs[r] = cmul(cscale(qs[r], a.scale), make_float2(cs, -sn));
+  }
+  __syncthreads();  // every wave is done with gl before the transform writes its image
+  int tz = threadIdx.x;
+  asm volatile("" : "+v"(tz));
+  auto ld1 = [&](int, int r, int) { return qs[r]; };
+  float2* dst = U + (size_t)bc * a.ncbu * CBU * u_rows(a.Hout) + blk_u(c, 0, a.Hout);
+  auto sv1 = [&](int, int, int j, float2 v) {
+    const int r = j - a.out_r0;
+    if ((unsigned)r < (unsigned)a.Hout) dst[u_roff(r)] = v;
+  };
+  fft_pow2_io<true, PN, TT, FFT_TAIL, false, false>(lds, twl, tz, ld1, sv1);
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // RSC (Props/RSC_Prop.py:129-215): transfer function = FFT2 of the spatial RS kernel on the
@@ -1575,6 +1759,11 @@ static int ensure_lds_attr() {
     add_slice_kernels<8192>(ks);
     add_slice_kernels<16384>(ks);
     ks.push_back((const void*)asm_rows_slice<0>);
+    ks.push_back((const void*)asm_cols_slice_adj<1024>);
+    ks.push_back((const void*)asm_cols_slice_adj<2048>);
+    ks.push_back((const void*)asm_cols_slice_adj<4096>);
+    ks.push_back((const void*)asm_cols_slice_adj<8192>);
+    ks.push_back((const void*)asm_cols_slice_adj<16384>);
     for (const void* k : ks) {
       hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
       if (e != hipSuccess) err = e;
@@ -1880,11 +2069,68 @@ static int run_slice(AsmArgs a, const AsmGeom& g, int Z, int R, const void* in, 
   return THZ_OK;
 }
 
+#define THZ_SLICE_ADJ_COLS(n, ...)                                                                 \
+  switch (n) {                                                                                     \
+    case 1024: hipLaunchKernelGGL(asm_cols_slice_adj<1024>, __VA_ARGS__); break;                   \
+    case 2048: hipLaunchKernelGGL(asm_cols_slice_adj<2048>, __VA_ARGS__); break;                   \
+    case 4096: hipLaunchKernelGGL(asm_cols_slice_adj<4096>, __VA_ARGS__); break;                   \
+    case 8192: hipLaunchKernelGGL(asm_cols_slice_adj<8192>, __VA_ARGS__); break;                   \
+    default: hipLaunchKernelGGL(asm_cols_slice_adj<16384>, __VA_ARGS__); break;                    \
+  }
+
+// the slice adjoint's workspace (g: the geometry of the adjoint descriptor, Hout x Wout the field):
+// the gradient spectrum U of one plane, in the layout asm_rows_inv reads, and Gv [Z][BC][ncb CB]
+static size_t slice_adj_u_bytes(const AsmGeom& g) {
+  return align256((size_t)g.BC * g.ncbu * CBU * u_rows(g.Hout) * sizeof(float2));
+}
+static size_t slice_adj_ws_bytes(const AsmGeom& g, int Z) {
+  return slice_adj_u_bytes(g) + align256((size_t)Z * g.BC * g.ncb * CB * sizeof(float2));
+}
+
+// row pass over the Z BC cotangent rows, the Z-summing column pass, asm_rows_inv once
+static int run_slice_adjoint(AsmArgs a, const AsmGeom& g, int Z, int R, const void* gout, void* gin, float2* U,
+                             float2* Gv, hipStream_t s, FftPlan pw, FftPlan ph) {
+  int e;
+  if ((e = ensure_lds_attr())) return e;
+  a.tab_blocks = 0;
+  a.zoff = 0;
+  a.nz = Z;
+  {
+    // each cotangent row is a one-row plane: Gv[z][bc] is T of plane z BC + bc with Hin = 1
+    KernelTimer kt("asm_rows_fwd", s);
+    AsmArgs a1 = a;
+    a1.Hin = 1;
+    a1.in_r0 = 0;
+    THZ_ROWS_SWITCH(g.Pw, asm_rows_fwd, dim3(Z * g.BC), fft_lds_bytes_io(g.Pw), s, (const float2*)gout, Gv, pw, a1);
+    THZ_LAUNCH_CHECK();
+    kt.stop();
+  }
+  {
+    KernelTimer kt("asm_cols_slice_adj", s);
+    const size_t lds2 = fft_lds_bytes(g.Ph) + 12 * THZ_MAX_Z;  // mz, zok and the z values, as asm_cols_slice
+    a.zrec = !plane_recurrence_disabled();
+    THZ_SLICE_ADJ_COLS(g.Ph, dim3(g.ncols * g.BC), dim3(threads_for(g.Ph)), lds2, s, (const float2*)Gv, U, ph, a, R);
+    THZ_LAUNCH_CHECK();
+    kt.stop();
+  }
+  a.nz = 1;
+  {
+    KernelTimer kt("asm_rows_inv", s);
+    THZ_ROWS_SWITCH(g.Pw, asm_rows_inv, dim3(g.BC * g.Hout), fft_lds_bytes_io(g.Pw), s, (const float2*)U, (float2*)gin,
+                    pw, a);
+    THZ_LAUNCH_CHECK();
+    kt.stop();
+  }
+  return THZ_OK;
+}
+
 // what thz_asm_slice_* accept, checked on the host before any device call
-static int validate_slice(const thz_asm_desc* d) {
+static int validate_slice(const thz_asm_desc* d, bool adjoint = false) {
   int e = validate(d);
   if (e) return e;
-  if (d->adjoint) return fail(THZ_E_UNSUPPORTED, "z-x slice: forward only (no adjoint)");
+  if (adjoint && d->adjoint != 1) return fail(THZ_E_ARG, "the z-x slice adjoint takes adjoint == 1");
+  if (!adjoint && d->adjoint)
+    return fail(THZ_E_UNSUPPORTED, "z-x slice: forward only (the adjoint is thz_asm_slice_adjoint)");
   if (d->z_dev) return fail(THZ_E_UNSUPPORTED, "z-x slice: host plane distances only (z_dev is not read)");
   if (!d->z) return fail(THZ_E_ARG, "null z");
   if (d->window_mask) return fail(THZ_E_UNSUPPORTED, "z-x slice: no window mask (apply the aperture separately)");
@@ -1943,6 +2189,53 @@ extern "C" int thz_asm_slice_forward(const thz_asm_desc* d, int row, const void*
   float2* T = (float2*)workspace;
   float2* V = (float2*)((char*)workspace + t_bytes(g));
   return run_slice(a, g, d->Z, row + a.out_r0, in, out, T, V, (hipStream_t)stream, pw, ph);
+}
+
+extern "C" int thz_asm_slice_adjoint_workspace_size(const thz_asm_desc* d, size_t* bytes) {
+  int e = validate_slice(d, true);
+  if (e) return e;
+  if (!bytes) return fail(THZ_E_ARG, "null bytes");
+  AsmGeom g;
+  geometry(d, &g);
+  *bytes = slice_adj_ws_bytes(g, d->Z);
+  return THZ_OK;
+}
+
+extern "C" int thz_asm_slice_adjoint(const thz_asm_desc* d, int row, const void* grad_out, void* grad_in,
+                                     void* workspace, size_t workspace_bytes, thz_stream_t stream) {
+  int e = validate_slice(d, true);
+  if (e) return e;
+  AsmGeom g;
+  geometry(d, &g);  // adjoint: Hin x Win the forward's output grid, Hout x Wout the field
+  if (row < 0 || row >= g.Hin) return fail(THZ_E_ARG, "z-x slice adjoint: row %d outside [0, %d)", row, g.Hin);
+  if (!grad_out || !grad_in) return fail(THZ_E_ARG, "null data pointer");
+  const size_t need = slice_adj_ws_bytes(g, d->Z);
+  if (!workspace || workspace_bytes < need)
+    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  FftPlan pw, ph;
+  if ((e = get_plan(g.Pw, &pw))) return e;
+  if ((e = get_plan(g.Ph, &ph))) return e;
+  AsmArgs a{};
+  a.BC = g.BC;
+  a.C = d->C;
+  a.Ph = g.Ph;
+  a.Pw = g.Pw;
+  a.in_r0 = d->unpad ? d->pad_h : 0; a.in_c0 = d->unpad ? d->pad_w : 0; a.Hin = g.Hin; a.Win = g.Win;
+  a.out_r0 = d->pad_h; a.out_c0 = d->pad_w; a.Hout = g.Hout; a.Wout = g.Wout;
+  a.ncols = g.ncols;
+  a.ncb = g.ncb;
+  a.ncbu = g.ncbu;
+  a.J = g.J;
+  a.bl = d->bandlimit;
+  a.adjoint = 1;
+  a.dx = d->dx;
+  a.dy = d->dy;
+  a.scale = (float)(1.0 / ((double)g.Ph * (double)g.Pw));
+  for (int c = 0; c < d->C; ++c) a.lam[c] = d->wavelengths[c];
+  for (int zi = 0; zi < d->Z; ++zi) a.zv[zi] = d->z[zi];
+  float2* U = (float2*)workspace;
+  float2* Gv = (float2*)((char*)workspace + slice_adj_u_bytes(g));
+  return run_slice_adjoint(a, g, d->Z, row + a.in_r0, grad_out, grad_in, U, Gv, (hipStream_t)stream, pw, ph);
 }
 
 extern "C" int thz_asm_band(const thz_asm_desc* d, int* ncols, int* z_chunk) {

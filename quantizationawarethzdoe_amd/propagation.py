@@ -136,7 +136,8 @@ def asm_slice_native(padded_height):
 def asm_slice_apply(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, out=None):
     """Raw launch of the z-x slice (thz_asm_slice_forward): data [B,C,H,W] complex64 -> [Z,B,C,Wo],
     output row ``row`` of every plane of ``zs`` (at most THZ_MAX_Z), equal to
-    asm_apply(...)[:, :, :, row, :] without forming the planes.  Forward only, not differentiable."""
+    asm_apply(...)[:, :, :, row, :] without forming the planes.  Forward only; asm_propagate_zx is the
+    differentiable form (backward: asm_slice_adjoint)."""
     _require_device(data, "ASM slice")
     if data.dtype != torch.complex64:
         raise TypeError(f"ASM slice kernels compute in complex64; got {data.dtype}")
@@ -157,6 +158,60 @@ def asm_slice_apply(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, ba
                                            ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
                                            ctypes.c_size_t(ws.numel()), _stream_handle()))
     return out
+
+
+def asm_slice_adjoint(g, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, height):
+    """Raw launch of the z-x slice's adjoint (thz_asm_slice_adjoint): the cotangent g [Z,B,C,Wo]
+    complex64 of asm_slice_apply(x [B,C,height,W], ..., row, ...) -> [B,C,height,W], the sum over the
+    planes of each plane's adjoint -- asm_apply(g placed at row ``row`` of zero planes, adjoint=True)
+    without forming the planes.  ``height`` is the field's H (g does not carry it).  At most
+    THZ_MAX_Z planes."""
+    _require_device(g, "ASM slice adjoint")
+    if g.dtype != torch.complex64:
+        raise TypeError(f"ASM slice kernels compute in complex64; got {g.dtype}")
+    L = _lib.lib()
+    g = g.contiguous()
+    Z, B, C, Wo = g.shape
+    if Z != len(zs):
+        raise ValueError(f"ASM slice adjoint: {Z} gradient rows for {len(zs)} z values")
+    H, W = int(height), Wo - (0 if unpad else 2 * pad_w)
+    d = _asm_desc(B, C, H, W, pad_h, pad_w, unpad, bandlimit, wavelengths, spacing, zs, True)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.thz_asm_slice_adjoint_workspace_size(ctypes.byref(d), ctypes.byref(nbytes)))
+    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=g.device)
+    gin = torch.empty((B, C, H, W), dtype=torch.complex64, device=g.device)
+    with torch.cuda.device(g.device):
+        _lib.check(L.thz_asm_slice_adjoint(ctypes.byref(d), int(row), ctypes.c_void_p(g.data_ptr()),
+                                           ctypes.c_void_p(gin.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                           ctypes.c_size_t(ws.numel()), _stream_handle()))
+    return gin
+
+
+class _AsmSliceFunction(torch.autograd.Function):
+    """The z-x slice with its native backward: forward asm_slice_apply, backward asm_slice_adjoint.
+    A linear map: nothing is saved but the configuration."""
+
+    @staticmethod
+    def forward(ctx, data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit):
+        ctx.cfg = (wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, data.shape[-2])
+        return asm_slice_apply(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit)
+
+    @staticmethod
+    def backward(ctx, g):
+        wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, height = ctx.cfg
+        gin = asm_slice_adjoint(g, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, height)
+        return gin, None, None, None, None, None, None, None, None
+
+
+def asm_propagate_zx(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad=True, bandlimit="exact"):
+    """Differentiable z-x slice on the slice kernels, forward and backward: [B,C,H,W] complex64 ->
+    [Z,B,C,Wo], output row ``row`` of every plane of ``zs`` (any length: chunks of THZ_MAX_Z planes).
+    The padded height must be one the slice kernels serve (asm_slice_native)."""
+    bl = _lib.BANDLIMIT[bandlimit] if not isinstance(bandlimit, int) else bandlimit
+    wl, sp, zs = list(map(float, wavelengths)), tuple(map(float, spacing)), list(map(float, zs))
+    outs = [_AsmSliceFunction.apply(data, wl, sp, zs[k:k + _lib.THZ_MAX_Z], int(row), int(pad_h), int(pad_w),
+                                    bool(unpad), bl) for k in range(0, len(zs), _lib.THZ_MAX_Z)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
 def _asm64_apply(data, wavelengths, spacing, zs, pad_h, pad_w, unpad, bandlimit, adjoint=False, out=None):
