@@ -378,16 +378,16 @@ __device__ __forceinline__ bool recurrence_step_ok(float z0, float z1, float zp,
          (double)eps == (double)step - (double)dz && fabs((double)eps) * (double)kl <= 1e-4;
 }
 
-// ZSUM: the Z-summing adjoint's column pass (a separate instantiation, so the forward's register
-// allocation is untouched by it).
-template <int PN, bool ZSUM>
-__device__ __forceinline__ void asm_cols_body(const float2* __restrict__ T, float2* __restrict__ U, FftPlan ph,
-                                              AsmArgs a) {
-  extern __shared__ float2 lds[];
-  // Tasks: the first kfull blocks are whole columns (all nz planes; full dispatch rounds of the
-  // resident-workgroup count), the last partial round's columns are split into kparts z-ranges
-  // so that round is short instead of a whole column pass on a few CUs.
-  int id, z_lo = 0, z_hi = a.nz;
+// What H_z is for the power-of-two column kernels (asm_cols, asm_cols_slice, asm_cols_slice_adj)
+// and the mixed-radix tables: each piece is written once here, in the fp32 operation order the
+// planes carry, so the slice and its adjoint apply the very H the full planes do.
+
+// The column task of this workgroup: the first kfull blocks are whole columns (all nz planes; full
+// dispatch rounds of the resident-workgroup count), the last partial round's columns are split
+// into kparts z-ranges so that round is short instead of a whole column pass on a few CUs.
+__device__ __forceinline__ void k2_task(const AsmArgs& a, int& id, int& z_lo, int& z_hi) {
+  z_lo = 0;
+  z_hi = a.nz;
   if ((int)blockIdx.x < a.kfull) {
     id = xcd_chunk(blockIdx.x, a.kfull);
   } else {
@@ -396,6 +396,143 @@ __device__ __forceinline__ void asm_cols_body(const float2* __restrict__ T, floa
     z_lo = part * a.nz / a.kparts;
     z_hi = (part + 1) * a.nz / a.kparts;
   }
+}
+
+// the column pass's LDS behind the transform image and the twiddles: per plane of the task the
+// kept-row bound M_z, the recurrence_votes bits and the z value (k2_lds_bytes on the host)
+struct ColLds {
+  int *mz, *zok;
+  float* zl;
+};
+template <int PN>
+__device__ __forceinline__ ColLds col_lds(float2* lds) {
+  int* mz = reinterpret_cast<int*>(lds + lds_floats2(PN) + tw_lds_count(PN));
+  return {mz, mz + THZ_MAX_Z, reinterpret_cast<float*>(mz + 2 * THZ_MAX_Z)};
+}
+
+// The evanescent and band-limit masks are monotone in |m_x| (every fp32 operation of
+// Props/ASM_Prop.py:245-306 is monotone), so the kept rows of the column Ky at the plane of s are
+// exactly |m_x| <= M_z: M_z by bisection with the exact reference-order tests, -1 when no row passes.
+// P = PN as the caller holds it: a.Ph in the column kernels, the constant in tf_tables_body (with
+// a.Ph there asm_rows_fwd<300, true> took 37 VGPRs for 36).
+template <int PN>
+__device__ __forceinline__ int tf_band_bound(const AsmArgs& a, int P, const TfScalars& s, float Ky) {
+  int lo = -1, hi = PN / 2 + 1;
+  const int bl = a.bl;
+  const float dx = a.dx;
+  if (tf_pass(bl, P, dx, s, Ky, 0)) {
+    lo = 0;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (tf_pass(bl, P, dx, s, Ky, mid)) lo = mid;
+      else hi = mid;
+    }
+  }
+  return lo;
+}
+
+// Plane q of a range of n planes with the z values zv(0 .. n-1).  Bit 0: q is reached from q - 1 in
+// ascending order; bit 1: from q + 1 in descending order (the range's last plane first); bit 2 (on
+// plane 0): |z| falls along the range (a sweep towards the aperture).
+template <class ZV>
+__device__ __forceinline__ int recurrence_votes(ZV zv, int q, int n, float kl) {
+  const bool fwd = q == 0 || (n >= 2 && recurrence_step_ok(zv(0), zv(1), zv(q - 1), zv(q), kl));
+  const bool bwd = q == n - 1 || (n >= 2 && recurrence_step_ok(zv(n - 1), zv(n - 2), zv(q + 1), zv(q), kl));
+  const bool inward = q == 0 && fabsf(zv(n - 1)) < fabsf(zv(0));
+  return (fwd ? 1 : 0) | (bwd ? 2 : 0) | (inward ? 4 : 0);
+}
+
+// The plane recurrence for a range of n planes (mz, zok: the range's M_z and votes in LDS)?  rec:
+// yes; rev: run it from the range's last plane.  One plane per lane, every wave voting on its own
+// copy (no loop over the planes per thread, no extra barrier); the votes are wave-uniform.
+template <int PN>
+__device__ __forceinline__ void recurrence_order(const int* mz, const int* zok, int n, int zrec, bool& rec,
+                                                 bool& rev) {
+  rec = rev = false;
+  if (!zrec || n < 3) return;
+  bool okf = true, okr = true, wide = false;
+  const int lane = threadIdx.x & 63;
+  for (int q0 = 0; q0 < n; q0 += 64) {
+    const int q = q0 + lane;
+    bool pf = true, pr = true, pw = false;
+    if (q < n) {
+      // the band may only narrow in the order the planes are run (an element that leaves it is
+      // zeroed in the recurrence for good): ascending order for a band that narrows with the plane
+      // index (cfg2's increasing z), descending order for one that widens (a decreasing z-sweep)
+      const int m = mz[q], mp = q > 0 ? mz[q - 1] : m, zk = zok[q];
+      pf = (zk & 1) && m <= mp;
+      pr = (zk & 2) && m >= mp;
+      pw = m >= PN / 4;  // a kept row with |m_x| >= PN/4: the recurrence keeps the values r < 4, r >= 12 only
+    }
+    okf = okf && __ballot(!pf) == 0;
+    okr = okr && __ballot(!pr) == 0;
+    wide = wide || __ballot(pw) != 0;
+  }
+  rec = (okf || okr) && !wide;
+  // a band constant over the range allows both orders: run the range from its plane nearest the
+  // aperture, as every column with a changing band of the same sweep does (read wave-uniform: the
+  // plane order, and with it every plane index and z of the z loop, stays in scalar registers)
+  const int zk0 = __builtin_amdgcn_readfirstlane(zok[0]);
+  rev = rec && okr && (!okf || (zk0 & 4));
+}
+
+// sqrt(k^2 - Kx^2 - Ky^2) of spectral element i of the column (z-independent)
+template <int PN>
+__device__ __forceinline__ float col_sq(int i, const AsmArgs& a, float kl2, float Ky2) {
+  const float Kx = kfreq(freq_index(i, PN), PN, a.dx);
+  return sqrtf(fmaxf(tf_sub(kl2, tf_add(tf_mul(Kx, Kx), Ky2)), 0.0f));
+}
+
+// H_z = exp(i z sq) (conj: its conjugate) by the hardware sincos: the per-plane form, and the
+// recurrence's anchor on the first plane it runs
+__device__ __forceinline__ float2 tf_cis(float z, float sq, bool conj) {
+  float sn, cs;
+  sincos_hw(tf_mul(z, sq), &sn, &cs);
+  return make_float2(cs, conj ? -sn : sn);
+}
+// the recurrence's step factor D = exp(i dz sq), formed in double and rounded once
+__device__ __forceinline__ float2 rec_step_factor(float dz, float sq, bool conj) {
+  const float2 d = cis_dd((double)dz * (double)sq);
+  return make_float2(d.x, conj ? -d.y : d.y);
+}
+// g (1 + i th), th = eps sq: the recurrence's correction of a step that is not dz exactly
+__device__ __forceinline__ float2 rec_correct(float2 g, float th) {
+  return make_float2(fmaf(-th, g.y, g.x), fmaf(th, g.x, g.y));
+}
+// The recurrence keeps value r (r < 4 or r >= 12) of thread tid, element tid + r PN/16 with
+// m_x = tid + r PN/16 (r < 4), tid + r PN/16 - PN (r >= 12), while |m_x| <= Ms
+template <int PN>
+__device__ __forceinline__ bool rec_keep(int r, int tid, int Ms) {
+  return r < 4 ? tid <= Ms - r * (PN / 16) : tid >= PN - r * (PN / 16) - Ms;
+}
+// slot of kept value r among the eight the slice kernels hold apart (r < 4: 0..3, r >= 12: 4..7)
+__host__ __device__ constexpr int rec_kslot(int r) { return r < 4 ? r : r - 8; }
+// The per-plane sincos form takes value r of a plane with the kept band M (Ms: its wave-uniform copy)?
+// r in [4, 12) are the rows PN/4 <= |m_x| < 3 PN/4: none kept where M < PN/4, skipped on a scalar branch.
+template <int PN>
+__device__ __forceinline__ bool sincos_keep(int r, int tid, int M, int Ms) {
+  if (r >= 4 && r < 12 && Ms < PN / 4) return false;
+  const int mx = freq_index(tid + r * (PN / 16), PN);
+  return !(mx > M || -mx > M);
+}
+// exp(2 pi i ((m R) mod PN) / PN) of the slice's row R at element m = tid + r PN/16: m R reduced in
+// integers (m, R < 2^14) and the angle in half-turns, both exact, so R = PN / 2 gives exactly +-1
+template <int PN>
+__device__ __forceinline__ float2 slice_row_phase(int tid, int r, int R) {
+  const int k = ((tid + r * (PN / 16)) * R) & (PN - 1);
+  float sn, cs;
+  sincospif((float)(2 * k) / (float)PN, &sn, &cs);
+  return make_float2(cs, sn);
+}
+
+// ZSUM: the Z-summing adjoint's column pass (a separate instantiation, so the forward's register
+// allocation is untouched by it).
+template <int PN, bool ZSUM>
+__device__ __forceinline__ void asm_cols_body(const float2* __restrict__ T, float2* __restrict__ U, FftPlan ph,
+                                              AsmArgs a) {
+  extern __shared__ float2 lds[];
+  int id, z_lo, z_hi;
+  k2_task(a, id, z_lo, z_hi);
   const int bc = id / a.ncols, c = id - bc * a.ncols;
   const int nt = blockDim.x;
   const int Ph = a.Ph;
@@ -446,94 +583,32 @@ __device__ __forceinline__ void asm_cols_body(const float2* __restrict__ T, floa
       fft_pow2_io<true, PN, TT, FFT_TAIL, false, false>(lds, twl, tz, ld1, sv1);
       return;
     }
-    // The evanescent and band-limit masks are monotone in |m_x| (every fp32 operation of
-    // Props/ASM_Prop.py:245-306 is monotone), so for each z the kept rows of this column are
-    // exactly |m_x| <= M_z.  One lane per z finds M_z by bisection with the exact
-    // reference-order tests; the per-element work is then sqrt once per column and one
-    // sincos per z.
-    int* mz = reinterpret_cast<int*>(lds + lds_floats2(PN) + tw_lds_count(PN));
+    // One lane per z finds the kept rows |m_x| <= M_z (tf_band_bound); the per-element work is
+    // then sqrt once per column and one sincos per z.  zl: the chunk's z values, staged next to
+    // mz for the z-loop of the forward (an LDS read per plane instead of a dependent global load
+    // at the top of every plane).
+    const auto [mz, zok, zl] = col_lds<PN>(lds);
     const float kl = TWO_PI_F / lam;
     const float kl2 = tf_mul(kl, kl);
     const float Ky2 = tf_mul(Ky, Ky);
     // strided over the chunk: a z_chunk may exceed the workgroup (64 threads at P = 1024)
-    int* zok = mz + THZ_MAX_Z;  // plane recurrence allowed at this plane (below)
-    // the chunk's z values, staged next to mz for the z-loop of the forward (an LDS read per
-    // plane instead of a dependent global load at the top of every plane)
-    float* zl = reinterpret_cast<float*>(zok + THZ_MAX_Z);
     for (int zz = tid; zz < z_hi - z_lo; zz += nt) {
       const float zq = zval(a, a.zoff + z_lo + zz);
       if constexpr (!ZSUM) zl[zz] = zq;
-      const TfScalars s = tf_scalars(a, lam, zq);
-      int lo = -1, hi = PN / 2 + 1;
-      const int bl = a.bl, P = a.Ph;
-      const float dx = a.dx;
-      if (tf_pass(bl, P, dx, s, Ky, 0)) {
-        lo = 0;
-        while (hi - lo > 1) {
-          const int mid = (lo + hi) >> 1;
-          if (tf_pass(bl, P, dx, s, Ky, mid)) lo = mid;
-          else hi = mid;
-        }
-      }
-      mz[zz] = lo;
-      if constexpr (!ZSUM) {
-        // bit 0: plane zz is reached from zz - 1 in ascending order; bit 1: from zz + 1 in
-        // descending order (the range's last plane first)
-        const int nzr = z_hi - z_lo;
-        auto zv = [&](int q) { return zval(a, a.zoff + z_lo + q); };
-        const bool fwd = zz == 0 || (nzr >= 2 && recurrence_step_ok(zv(0), zv(1), zv(zz - 1), zv(zz), kl));
-        const bool bwd = zz == nzr - 1 ||
-                         (nzr >= 2 && recurrence_step_ok(zv(nzr - 1), zv(nzr - 2), zv(zz + 1), zv(zz), kl));
-        // bit 2 (on plane 0): |z| falls along the range (a sweep towards the aperture)
-        const bool inward = zz == 0 && fabsf(zv(nzr - 1)) < fabsf(zv(0));
-        zok[zz] = (fwd ? 1 : 0) | (bwd ? 2 : 0) | (inward ? 4 : 0);
-      }
+      mz[zz] = tf_band_bound<PN>(a, a.Ph, tf_scalars(a, lam, zq), Ky);
+      if constexpr (!ZSUM)
+        zok[zz] = recurrence_votes([&](int q) { return zval(a, a.zoff + z_lo + q); }, zz, z_hi - z_lo, kl);
     }
-    // sqrt(k^2 - Kx^2 - Ky^2) of the elements this thread holds: z-independent, computed once
-    // per column (the per-z work is then one product and one sincos per element)
+    // sq of the elements this thread holds, computed once per column
     float sq[MBL][RL];
 #pragma unroll
     for (int m = 0; m < MBL; ++m)
 #pragma unroll
-      for (int r = 0; r < RL; ++r) {
-        const float Kx = kfreq(freq_index(tid + m * TT + r * (PN / RL), PN), PN, a.dx);
-        sq[m][r] = sqrtf(fmaxf(tf_sub(kl2, tf_add(tf_mul(Kx, Kx), Ky2)), 0.0f));
-      }
+      for (int r = 0; r < RL; ++r) sq[m][r] = col_sq<PN>(tid + m * TT + r * (PN / RL), a, kl2, Ky2);
     __syncthreads();  // mz visible
     // the plane recurrence (below) for this column?
     bool rec = false, rev = false;
-    if constexpr (!ZSUM && RL == 16 && MBL == 1) {
-      if (a.zrec && z_hi - z_lo >= 3) {
-        // one plane per lane, every wave voting on its own copy (no loop over the planes per
-        // thread, no extra barrier); the votes are wave-uniform
-        bool okf = true, okr = true, wide = false;
-        const int lane = threadIdx.x & 63;
-        for (int q0 = 0; q0 < z_hi - z_lo; q0 += 64) {
-          const int q = q0 + lane;
-          bool pf = true, pr = true, pw = false;
-          if (q < z_hi - z_lo) {
-            // the band may only narrow in the order the planes are run (an element that leaves
-            // it is zeroed in the recurrence for good, below): ascending order for a band that
-            // narrows with the plane index (cfg2's increasing z), descending order for one that
-            // widens (a decreasing z-sweep)
-            const int m = mz[q], mp = q > 0 ? mz[q - 1] : m, zk = zok[q];
-            pf = (zk & 1) && m <= mp;
-            pr = (zk & 2) && m >= mp;
-            pw = m >= PN / 4;
-          }
-          okf = okf && __ballot(!pf) == 0;
-          okr = okr && __ballot(!pr) == 0;
-          wide = wide || __ballot(pw) != 0;
-        }
-        rec = (okf || okr) && !wide;
-        // a band constant over the range allows both orders: run the range from its plane nearest
-        // the aperture, as every column with a changing band of the same sweep does
-        // (read wave-uniform: the plane order, and with it every plane index and z of the loop
-        // below, stays in scalar registers)
-        const int zk0 = __builtin_amdgcn_readfirstlane(zok[0]);
-        rev = rec && okr && (!okf || (zk0 & 4));
-      }
-    }
+    if constexpr (!ZSUM && RL == 16 && MBL == 1) recurrence_order<PN>(mz, zok, z_hi - z_lo, a.zrec, rec, rev);
     if constexpr (ZSUM) {
       // adjoint over the chunk's planes: sp = sum_z FFT(T_z column) conj(H_z), then one inverse
 #pragma unroll
@@ -601,11 +676,8 @@ __device__ __forceinline__ void asm_cols_body(const float2* __restrict__ T, floa
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           if (r >= 4 && r < 12) continue;
-          float sn, cs;
-          sincos_hw(tf_mul(z0, sq[0][r]), &sn, &cs);
-          sp[0][r] = cmul(sp[0][r], make_float2(cs, a.adjoint ? -sn : sn));
-          const float2 d = cis_dd((double)dz * (double)sq[0][r]);
-          sp[0][rec_dslot(r)] = make_float2(d.x, a.adjoint ? -d.y : d.y);
+          sp[0][r] = cmul(sp[0][r], tf_cis(z0, sq[0][r], a.adjoint));
+          sp[0][rec_dslot(r)] = rec_step_factor(dz, sq[0][r], a.adjoint);
           if (a.adjoint) sq[0][r] = -sq[0][r];
           // one element's double-precision evaluation at a time (all eight interleaved need more
           // registers than the kernel has)
@@ -631,9 +703,7 @@ __device__ __forceinline__ void asm_cols_body(const float2* __restrict__ T, floa
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               if (r >= 4 && r < 12) continue;
-              const float2 g = sp[0][r];
-              const float th = eps * sq[0][r];
-              sp[0][r] = make_float2(fmaf(-th, g.y, g.x), fmaf(th, g.x, g.y));
+              sp[0][r] = rec_correct(sp[0][r], eps * sq[0][r]);  // sq holds -sq for the adjoint
             }
           }
         }
@@ -651,9 +721,7 @@ __device__ __forceinline__ void asm_cols_body(const float2* __restrict__ T, floa
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             if (r >= 4 && r < 12) continue;
-            // element tz + r PN/16: m_x = tz + r PN/16 (r < 4), tz + r PN/16 - PN (r >= 12)
-            const bool keep = r < 4 ? tz <= Ms - r * (PN / 16) : tz >= PN - r * (PN / 16) - Ms;
-            if (!keep) sp[0][r] = make_float2(0.f, 0.f);
+            if (!rec_keep<PN>(r, tz, Ms)) sp[0][r] = make_float2(0.f, 0.f);
           }
         }
         Mprev = Ms;
@@ -664,6 +732,7 @@ __device__ __forceinline__ void asm_cols_body(const float2* __restrict__ T, floa
       // plane's kept band M is below PN/4 (all but the few columns near m_y = 0 at cfg2) they are
       // zero for every thread, and a scalar branch skips their sincos and product
       const bool mid0 = Ms < PN / 4;
+      // (sincos_keep's two tests, inline: the recurrence's return sits between them)
       auto ld1 = [&](int m, int r, int idx) {
         if (RL == 16 && r >= 4 && r < 12 && mid0) return make_float2(0.f, 0.f);
         if constexpr (REC) {
@@ -671,9 +740,7 @@ __device__ __forceinline__ void asm_cols_body(const float2* __restrict__ T, floa
         }
         const int mx = freq_index(idx, PN);
         if (mx > M || -mx > M) return make_float2(0.f, 0.f);
-        float sn, cs;
-        sincos_hw(tf_mul(z, sq[m][r]), &sn, &cs);
-        return cmul(sp[m][r], make_float2(cs, a.adjoint ? -sn : sn));
+        return cmul(sp[m][r], tf_cis(z, sq[m][r], a.adjoint));
       };
       float2* dst = U + ((size_t)zz * a.BC + bc) * a.ncbu * CBU * u_rows(a.Hout) + blk_u(c, 0, a.Hout);
       auto sv1 = [&](int, int, int j, float2 v) {
@@ -785,10 +852,7 @@ __device__ __forceinline__ void tf_tables_body(const AsmArgs& a, int blk, int wi
     const float kl = TWO_PI_F / lam;
     const float kl2 = tf_mul(kl, kl);
     const float Ky2 = tf_mul(Ky, Ky);
-    for (int i = threadIdx.x; i < PN; i += blockDim.x) {
-      const float Kx = kfreq(freq_index(i, PN), PN, a.dx);
-      a.sqt[col * PN + i] = sqrtf(fmaxf(tf_sub(kl2, tf_add(tf_mul(Kx, Kx), Ky2)), 0.0f));
-    }
+    for (int i = threadIdx.x; i < PN; i += blockDim.x) a.sqt[col * PN + i] = col_sq<PN>(i, a, kl2, Ky2);
   }
   if (a.nz <= 2) {
     // few planes (the DONN / QAT layers: one): every lane tests ceil((PN/2+1)/64) rows and M_z + 1
@@ -806,19 +870,8 @@ __device__ __forceinline__ void tf_tables_body(const AsmArgs& a, int blk, int wi
     }
     return;
   }
-  for (int zz = threadIdx.x; zz < a.nz; zz += blockDim.x) {
-    const TfScalars s = tf_scalars(a, lam, zval(a, a.zoff + zz));
-    int lo = -1, hi = PN / 2 + 1;
-    if (tf_pass(a.bl, PN, a.dx, s, Ky, 0)) {
-      lo = 0;
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tf_pass(a.bl, PN, a.dx, s, Ky, mid)) lo = mid;
-        else hi = mid;
-      }
-    }
-    a.mzt[col * a.nz + zz] = lo;
-  }
+  for (int zz = threadIdx.x; zz < a.nz; zz += blockDim.x)
+    a.mzt[col * a.nz + zz] = tf_band_bound<PN>(a, PN, tf_scalars(a, lam, zval(a, a.zoff + zz)), Ky);
 }
 
 template <int PN>
@@ -839,15 +892,8 @@ __device__ __forceinline__ void asm_cols_mx_body(const float2* __restrict__ T, f
   constexpr int PN = MP::N, RL = MP::RL, MT = mx_threads(PN), NBL = PN / RL, MBL = (NBL + MT - 1) / MT;
   static_assert(MP::R0 == RL, "the inverse must start where the forward ends");
   extern __shared__ float2 lds[];
-  int id, z_lo = 0, z_hi = a.nz;
-  if ((int)blockIdx.x < a.kfull) {
-    id = xcd_chunk(blockIdx.x, a.kfull);
-  } else {
-    const int t = blockIdx.x - a.kfull, part = t % a.kparts;
-    id = a.kfull + t / a.kparts;
-    z_lo = part * a.nz / a.kparts;
-    z_hi = (part + 1) * a.nz / a.kparts;
-  }
+  int id, z_lo, z_hi;
+  k2_task(a, id, z_lo, z_hi);
   const int bc = id / a.ncols, c = id - bc * a.ncols;
   const float2* col = T + (size_t)bc * a.ncb * CB * a.Hin + blk(c, 0, a.Hin);
   int tid = threadIdx.x;
@@ -1115,13 +1161,12 @@ __global__ void __launch_bounds__(1024) THZ_ROW_ATTR asm_rows_inv_loss(const flo
 // budget (D rounded once, 6e-8 per plane) is stated for 64 planes
 constexpr int SLICE_ZC = 64;
 
-// The transfer-function side is asm_cols_body's forward (ZSUM = false, a.tft = nullptr): the same
-// tasks (whole columns, then the last dispatch round's columns split into z-ranges, k2_tasks), the
-// same tf_scalars / tf_pass band bisection, sq values, recurrence_step_ok votes, plane order, step
-// factors and band zeroing, in the same fp32 operation order -- so every plane's H carries the very
-// rounding it has in asm_cols (the recurrence starts from the same planes), and the slice differs
-// from the full planes' row by the summation alone.  Kept as a copy so that asm_cols' own code and
-// registers stay as they are.
+// The transfer-function side is asm_cols_body's forward (ZSUM = false, a.tft = nullptr) through the
+// same helpers (k2_task, tf_band_bound, recurrence_votes, recurrence_order, col_sq, tf_cis,
+// rec_step_factor, rec_correct, rec_keep), on the same tasks and z-chunks -- so every plane's H
+// carries the very rounding it has in asm_cols, and the slice differs from the full planes' row by
+// the summation alone.  Not shared: where the step factors live (dstep here, the spectrum's free
+// slots in asm_cols_body) and the z loop around them, which each kernel's register allocation shapes.
 template <int PN>
 __global__ void __launch_bounds__(1024) asm_cols_slice(const float2* __restrict__ T, float2* __restrict__ V,
                                                       FftPlan ph, AsmArgs a, int R) {
@@ -1129,15 +1174,8 @@ __global__ void __launch_bounds__(1024) asm_cols_slice(const float2* __restrict_
   using S = Pow2Sched<PN>;
   constexpr int TT = Geo<PN>::T;
   static_assert(S::radix(S::NST - 1, true) == 16 && PN / 16 / TT == 1, "one radix-16 butterfly per thread");
-  int id, z_lo = 0, z_hi = a.nz;
-  if ((int)blockIdx.x < a.kfull) {
-    id = xcd_chunk(blockIdx.x, a.kfull);
-  } else {
-    const int t = blockIdx.x - a.kfull, part = t % a.kparts;
-    id = a.kfull + t / a.kparts;
-    z_lo = part * a.nz / a.kparts;
-    z_hi = (part + 1) * a.nz / a.kparts;
-  }
+  int id, z_lo, z_hi;
+  k2_task(a, id, z_lo, z_hi);
   const int bc = id / a.ncols, c = id - bc * a.ncols;
   const int nt = blockDim.x, nz = z_hi - z_lo;  // this task's planes: z_lo + [0, nz) of the chunk
   const float2* col = T + (size_t)bc * a.ncb * CB * a.Hin + blk(c, 0, a.Hin);
@@ -1152,69 +1190,26 @@ __global__ void __launch_bounds__(1024) asm_cols_slice(const float2* __restrict_
   };
   auto sv0 = [&](int, int r, int, float2 v) { sp[r] = v; };
   fft_pow2_io<false, PN, TT, true, false, false>(lds, twl, tid, ld0, sv0);
-  // S'[m] = S[m] / (Ph Pw) exp(2 pi i ((m R) mod Ph) / Ph): the product reduced exactly in integers
-  // (m, R < 2^14), the angle in half-turns exact in fp32, so R = Ph / 2 gives exactly +-1
+  // S'[m] = S[m] / (Ph Pw) exp(2 pi i ((m R) mod Ph) / Ph)
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int k = ((tid + r * (PN / 16)) * R) & (PN - 1);
-    float sn, cs;
-    sincospif((float)(2 * k) / (float)PN, &sn, &cs);
-    sp[r] = cmul(cscale(sp[r], a.scale), make_float2(cs, sn));
-  }
-  int* mz = reinterpret_cast<int*>(lds + lds_floats2(PN) + tw_lds_count(PN));
-  int* zok = mz + THZ_MAX_Z;
-  float* zl = reinterpret_cast<float*>(zok + THZ_MAX_Z);
+  for (int r = 0; r < 16; ++r) sp[r] = cmul(cscale(sp[r], a.scale), slice_row_phase<PN>(tid, r, R));
+  const auto [mz, zok, zl] = col_lds<PN>(lds);
   const float kl = TWO_PI_F / lam;
   const float kl2 = tf_mul(kl, kl);
   const float Ky2 = tf_mul(Ky, Ky);
   for (int zz = tid; zz < nz; zz += nt) {
     const float zq = zval(a, a.zoff + z_lo + zz);
     zl[zz] = zq;
-    const TfScalars s = tf_scalars(a, lam, zq);
-    int lo = -1, hi = PN / 2 + 1;
-    if (tf_pass(a.bl, a.Ph, a.dx, s, Ky, 0)) {
-      lo = 0;
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tf_pass(a.bl, a.Ph, a.dx, s, Ky, mid)) lo = mid;
-        else hi = mid;
-      }
-    }
-    mz[zz] = lo;
-    auto zv = [&](int q) { return zval(a, a.zoff + z_lo + q); };
-    const bool fwd = zz == 0 || (nz >= 2 && recurrence_step_ok(zv(0), zv(1), zv(zz - 1), zv(zz), kl));
-    const bool bwd = zz == nz - 1 || (nz >= 2 && recurrence_step_ok(zv(nz - 1), zv(nz - 2), zv(zz + 1), zv(zz), kl));
-    const bool inward = zz == 0 && fabsf(zv(nz - 1)) < fabsf(zv(0));
-    zok[zz] = (fwd ? 1 : 0) | (bwd ? 2 : 0) | (inward ? 4 : 0);
+    mz[zz] = tf_band_bound<PN>(a, a.Ph, tf_scalars(a, lam, zq), Ky);
+    zok[zz] = recurrence_votes([&](int q) { return zval(a, a.zoff + z_lo + q); }, zz, nz, kl);
   }
   float sq[16];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const float Kx = kfreq(freq_index(tid + r * (PN / 16), PN), PN, a.dx);
-    sq[r] = sqrtf(fmaxf(tf_sub(kl2, tf_add(tf_mul(Kx, Kx), Ky2)), 0.0f));
-  }
+  for (int r = 0; r < 16; ++r) sq[r] = col_sq<PN>(tid + r * (PN / 16), a, kl2, Ky2);
   __syncthreads();  // mz, zok, zl visible; every wave is done with the transform's LDS image
-  bool rec = false, rev = false;
+  bool rec, rev;
+  recurrence_order<PN>(mz, zok, nz, a.zrec, rec, rev);
   const int lane = threadIdx.x & 63;
-  if (a.zrec && nz >= 3) {
-    bool okf = true, okr = true, wide = false;
-    for (int q0 = 0; q0 < nz; q0 += 64) {
-      const int q = q0 + lane;
-      bool pf = true, pr = true, pw = false;
-      if (q < nz) {
-        const int m = mz[q], mp = q > 0 ? mz[q - 1] : m, zk = zok[q];
-        pf = (zk & 1) && m <= mp;
-        pr = (zk & 2) && m >= mp;
-        pw = m >= PN / 4;
-      }
-      okf = okf && __ballot(!pf) == 0;
-      okr = okr && __ballot(!pr) == 0;
-      wide = wide || __ballot(pw) != 0;
-    }
-    rec = (okf || okr) && !wide;
-    const int zk0 = __builtin_amdgcn_readfirstlane(zok[0]);
-    rev = rec && okr && (!okf || (zk0 & 4));
-  }
   // each wave's partial sum of plane zz in slot [zz][wave] of the (now free) transform image;
   // the planes are finished after the loop in a fixed order (no barrier inside the z loop)
   float2* part = lds;
@@ -1230,11 +1225,9 @@ __global__ void __launch_bounds__(1024) asm_cols_slice(const float2* __restrict_
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       if (r >= 4 && r < 12) continue;
-      float sn, cs;
-      sincos_hw(tf_mul(z0, sq[r]), &sn, &cs);
-      sp[r] = cmul(sp[r], make_float2(cs, sn));
-      dstep[r < 4 ? r : r - 8] = cis_dd((double)dz * (double)sq[r]);
-      __builtin_amdgcn_sched_barrier(0);
+      sp[r] = cmul(sp[r], tf_cis(z0, sq[r], false));
+      dstep[rec_kslot(r)] = rec_step_factor(dz, sq[r], false);
+      __builtin_amdgcn_sched_barrier(0);  // one double evaluation at a time, as in asm_cols_body
     }
   }
   for (int it = 0; it < nz; ++it) {
@@ -1249,15 +1242,14 @@ __global__ void __launch_bounds__(1024) asm_cols_slice(const float2* __restrict_
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           if (r >= 4 && r < 12) continue;
-          sp[r] = cmul(sp[r], dstep[r < 4 ? r : r - 8]);
+          sp[r] = cmul(sp[r], dstep[rec_kslot(r)]);
         }
+        // skipped on a scalar branch where the step is dz exactly (60 of cfg2's 63 steps)
         if (__builtin_amdgcn_readfirstlane(__float_as_int(eps)) != 0) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             if (r >= 4 && r < 12) continue;
-            const float2 g = sp[r];
-            const float th = eps * sq[r];
-            sp[r] = make_float2(fmaf(-th, g.y, g.x), fmaf(th, g.x, g.y));
+            sp[r] = rec_correct(sp[r], eps * sq[r]);
           }
         }
       }
@@ -1266,8 +1258,7 @@ __global__ void __launch_bounds__(1024) asm_cols_slice(const float2* __restrict_
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           if (r >= 4 && r < 12) continue;
-          const bool keep = r < 4 ? tid <= Ms - r * (PN / 16) : tid >= PN - r * (PN / 16) - Ms;
-          if (!keep) sp[r] = make_float2(0.f, 0.f);
+          if (!rec_keep<PN>(r, tid, Ms)) sp[r] = make_float2(0.f, 0.f);
         }
       }
       Mprev = Ms;
@@ -1277,16 +1268,9 @@ __global__ void __launch_bounds__(1024) asm_cols_slice(const float2* __restrict_
         acc = cadd(acc, sp[r]);
       }
     } else {
-      const bool mid0 = Ms < PN / 4;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (r >= 4 && r < 12 && mid0) continue;
-        const int mx = freq_index(tid + r * (PN / 16), PN);
-        if (mx > M || -mx > M) continue;
-        float sn, cs;
-        sincos_hw(tf_mul(z, sq[r]), &sn, &cs);
-        acc = cadd(acc, cmul(sp[r], make_float2(cs, sn)));
-      }
+      for (int r = 0; r < 16; ++r)
+        if (sincos_keep<PN>(r, tid, M, Ms)) acc = cadd(acc, cmul(sp[r], tf_cis(z, sq[r], false)));
     }
     for (int o = 32; o > 0; o >>= 1) {
       acc.x += __shfl_xor(acc.x, o);
@@ -1348,11 +1332,12 @@ __global__ void __launch_bounds__(1024) asm_rows_slice(const float2* __restrict_
 // `a` is the adjoint's argument block (in_* the forward's output window, out_* its input window).
 // ---------------------------------------------------------------------------------------------
 // One whole-column task per (bc, c); the planes are summed in segments of SLICE_ZC planes, each
-// with the forward's own votes, plane order, anchor and step factors (the transfer-function side is
-// asm_cols_slice's, conjugated), so the recurrence never runs more than SLICE_ZC steps from a
-// sincos anchor.  Under the recurrence H_j = A prod_{k <= j} s_k (A the anchor, s_k = D (1 + i eps_k sq))
-// and the segment's sum is a polynomial in the conjugate steps, run as Horner steps from the
-// segment's far plane inward: acc = (acc + Gv_j) conj(s_j), and conj(A) once at the end.  The band
+// with the forward's own votes, plane order, anchor and step factors (asm_cols_slice's helpers,
+// conjugated; the Horner loop and its registers are this kernel's own), so the recurrence never
+// runs more than SLICE_ZC steps from a sincos anchor.  Under the recurrence H_j = A prod_{k <= j} s_k
+// (A the anchor, s_k = D (1 + i eps_k sq)) and the segment's sum is a polynomial in the conjugate
+// steps, run as Horner steps from the segment's far plane inward: acc = (acc + Gv_j) conj(s_j), and
+// conj(A) once at the end.  The band
 // only narrows in the order the planes are run, so an element enters the sum at the last plane
 // that still holds it.  Every sum runs in a fixed order in registers: two calls are bit-identical.
 template <int PN>
@@ -1373,9 +1358,7 @@ __global__ void __launch_bounds__(1024) asm_cols_slice_adj(const float2* __restr
   // the column's Gv values in the transform image (free until the inverse transform): read
   // wave-uniform in the z loops
   float2* gl = lds;
-  int* mz = reinterpret_cast<int*>(lds + lds_floats2(PN) + tw_lds_count(PN));
-  int* zok = mz + THZ_MAX_Z;
-  float* zl = reinterpret_cast<float*>(zok + THZ_MAX_Z);
+  const auto [mz, zok, zl] = col_lds<PN>(lds);
   const float kl = TWO_PI_F / lam;
   const float kl2 = tf_mul(kl, kl);
   const float Ky2 = tf_mul(Ky, Ky);
@@ -1383,53 +1366,22 @@ __global__ void __launch_bounds__(1024) asm_cols_slice_adj(const float2* __restr
     gl[zz] = Gv[((size_t)zz * a.BC + bc) * a.ncb * CB + c];
     const float zq = zval(a, zz);
     zl[zz] = zq;
-    const TfScalars s = tf_scalars(a, lam, zq);
-    int lo = -1, hi = PN / 2 + 1;
-    if (tf_pass(a.bl, a.Ph, a.dx, s, Ky, 0)) {
-      lo = 0;
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tf_pass(a.bl, a.Ph, a.dx, s, Ky, mid)) lo = mid;
-        else hi = mid;
-      }
-    }
-    mz[zz] = lo;
+    mz[zz] = tf_band_bound<PN>(a, a.Ph, tf_scalars(a, lam, zq), Ky);
     // the votes of the plane's own segment [s0, s0 + nzs), as asm_cols_slice takes them per launch
-    const int s0 = zz / SLICE_ZC * SLICE_ZC, nzs = min(SLICE_ZC, Z - s0), q = zz - s0;
-    auto zv = [&](int k) { return zval(a, s0 + k); };
-    const bool fwd = q == 0 || (nzs >= 2 && recurrence_step_ok(zv(0), zv(1), zv(q - 1), zv(q), kl));
-    const bool bwd = q == nzs - 1 || (nzs >= 2 && recurrence_step_ok(zv(nzs - 1), zv(nzs - 2), zv(q + 1), zv(q), kl));
-    const bool inward = q == 0 && fabsf(zv(nzs - 1)) < fabsf(zv(0));
-    zok[zz] = (fwd ? 1 : 0) | (bwd ? 2 : 0) | (inward ? 4 : 0);
+    const int s0 = zz / SLICE_ZC * SLICE_ZC, nzs = min(SLICE_ZC, Z - s0);
+    zok[zz] = recurrence_votes([&](int k) { return zval(a, s0 + k); }, zz - s0, nzs, kl);
   }
   float sq[16];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const float Kx = kfreq(freq_index(tid + r * (PN / 16), PN), PN, a.dx);
-    sq[r] = sqrtf(fmaxf(tf_sub(kl2, tf_add(tf_mul(Kx, Kx), Ky2)), 0.0f));
-  }
+  for (int r = 0; r < 16; ++r) sq[r] = col_sq<PN>(tid + r * (PN / 16), a, kl2, Ky2);
   __syncthreads();  // gl, mz, zok, zl visible
   float2 qs[16];    // Q, element tid + r PN/16
 #pragma unroll
   for (int r = 0; r < 16; ++r) qs[r] = make_float2(0.f, 0.f);
-  const int lane = threadIdx.x & 63;
   for (int s0 = 0; s0 < Z; s0 += SLICE_ZC) {
     const int nzs = min(SLICE_ZC, Z - s0);
-    bool rec = false, rev = false;
-    if (a.zrec && nzs >= 3) {
-      // one plane per lane (nzs <= 64), every wave voting on its own copy
-      bool pf = true, pr = true, pw = false;
-      if (lane < nzs) {
-        const int m = mz[s0 + lane], mp = lane > 0 ? mz[s0 + lane - 1] : m, zk = zok[s0 + lane];
-        pf = (zk & 1) && m <= mp;
-        pr = (zk & 2) && m >= mp;
-        pw = m >= PN / 4;
-      }
-      const bool okf = __ballot(!pf) == 0, okr = __ballot(!pr) == 0, wide = __ballot(pw) != 0;
-      rec = (okf || okr) && !wide;
-      const int zk0 = __builtin_amdgcn_readfirstlane(zok[s0]);
-      rev = rec && okr && (!okf || (zk0 & 4));
-    }
+    bool rec, rev;
+    recurrence_order<PN>(mz + s0, zok + s0, nzs, a.zrec, rec, rev);
     if (rec) {
       const int zfirst = rev ? s0 + nzs - 1 : s0, zstep = rev ? -1 : 1;
       const float z0 = zl[zfirst];
@@ -1438,10 +1390,9 @@ __global__ void __launch_bounds__(1024) asm_cols_slice_adj(const float2* __restr
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         if (r >= 4 && r < 12) continue;
-        const float2 d = cis_dd((double)dz * (double)sq[r]);
-        dstep[r < 4 ? r : r - 8] = make_float2(d.x, -d.y);
-        acc[r < 4 ? r : r - 8] = make_float2(0.f, 0.f);
-        __builtin_amdgcn_sched_barrier(0);
+        dstep[rec_kslot(r)] = rec_step_factor(dz, sq[r], true);
+        acc[rec_kslot(r)] = make_float2(0.f, 0.f);
+        __builtin_amdgcn_sched_barrier(0);  // one double evaluation at a time, as in asm_cols_slice
       }
       for (int it = nzs - 1; it >= 0; --it) {
         const int zz = zfirst + it * zstep;
@@ -1451,9 +1402,8 @@ __global__ void __launch_bounds__(1024) asm_cols_slice_adj(const float2* __restr
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           if (r >= 4 && r < 12) continue;
-          // element tid + r PN/16: m_x = tid + r PN/16 (r < 4), tid + r PN/16 - PN (r >= 12)
-          const bool keep = r < 4 ? tid <= Ms - r * (PN / 16) : tid >= PN - r * (PN / 16) - Ms;
-          float2& v = acc[r < 4 ? r : r - 8];
+          const bool keep = rec_keep<PN>(r, tid, Ms);
+          float2& v = acc[rec_kslot(r)];
           v.x += keep ? gx : 0.f;
           v.y += keep ? gy : 0.f;
         }
@@ -1467,9 +1417,7 @@ __global__ void __launch_bounds__(1024) asm_cols_slice_adj(const float2* __restr
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               if (r >= 4 && r < 12) continue;
-              const float2 g = acc[r < 4 ? r : r - 8];
-              const float th = eps * sq[r];
-              acc[r < 4 ? r : r - 8] = make_float2(fmaf(th, g.y, g.x), fmaf(-th, g.x, g.y));
+              acc[rec_kslot(r)] = rec_correct(acc[rec_kslot(r)], -(eps * sq[r]));
             }
           }
         }
@@ -1477,9 +1425,7 @@ __global__ void __launch_bounds__(1024) asm_cols_slice_adj(const float2* __restr
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         if (r >= 4 && r < 12) continue;
-        float sn, cs;
-        sincos_hw(tf_mul(z0, sq[r]), &sn, &cs);
-        qs[r] = cadd(qs[r], cmul(acc[r < 4 ? r : r - 8], make_float2(cs, -sn)));
+        qs[r] = cadd(qs[r], cmul(acc[rec_kslot(r)], tf_cis(z0, sq[r], true)));
       }
     } else {
       for (int zz = s0; zz < s0 + nzs; ++zz) {
@@ -1488,26 +1434,17 @@ __global__ void __launch_bounds__(1024) asm_cols_slice_adj(const float2* __restr
         const int Ms = __builtin_amdgcn_readfirstlane(M);
         const float gx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(gl[zz].x)));
         const float gy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(gl[zz].y)));
-        const bool mid0 = Ms < PN / 4;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          if (r >= 4 && r < 12 && mid0) continue;
-          const int mx = freq_index(tid + r * (PN / 16), PN);
-          if (mx > M || -mx > M) continue;
-          float sn, cs;
-          sincos_hw(tf_mul(z, sq[r]), &sn, &cs);
-          qs[r] = cadd(qs[r], cmul(make_float2(gx, gy), make_float2(cs, -sn)));
-        }
+        for (int r = 0; r < 16; ++r)
+          if (sincos_keep<PN>(r, tid, M, Ms)) qs[r] = cadd(qs[r], cmul(make_float2(gx, gy), tf_cis(z, sq[r], true)));
       }
     }
   }
-  // Q[m] = conj(exp(2 pi i ((m R) mod Ph) / Ph) / (Ph Pw)) x the sum: the angle as in asm_cols_slice
+  // Q[m] = conj(exp(2 pi i ((m R) mod Ph) / Ph) / (Ph Pw)) x the sum
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int k = ((tid + r * (PN / 16)) * R) & (PN - 1);
-    float sn, cs;
-    sincospif((float)(2 * k) / (float)PN, &sn, &cs);
-    qs[r] = cmul(cscale(qs[r], a.scale), make_float2(cs, -sn));
+    const float2 p = slice_row_phase<PN>(tid, r, R);
+    qs[r] = cmul(cscale(qs[r], a.scale), make_float2(p.x, -p.y));
   }
   __syncthreads();  // every wave is done with gl before the transform writes its image
   int tz = threadIdx.x;
@@ -1702,6 +1639,34 @@ static void geometry(const thz_asm_desc* d, AsmGeom* g) {
   g->adj = d->adjoint;
 }
 
+// The argument block as every ASM entry point starts it: sizes, the forward's windows or
+// (d->adjoint) the adjoint's, the band, spacings, scale, wavelengths and the planes.
+static AsmArgs asm_args_base(const thz_asm_desc* d, const AsmGeom& g) {
+  AsmArgs a{};
+  a.BC = g.BC;
+  a.C = d->C;
+  a.Ph = g.Ph;
+  a.Pw = g.Pw;
+  const int o_r0 = d->unpad ? d->pad_h : 0, o_c0 = d->unpad ? d->pad_w : 0;
+  a.in_r0 = d->adjoint ? o_r0 : d->pad_h; a.in_c0 = d->adjoint ? o_c0 : d->pad_w;
+  a.out_r0 = d->adjoint ? d->pad_h : o_r0; a.out_c0 = d->adjoint ? d->pad_w : o_c0;
+  a.Hin = g.Hin; a.Win = g.Win; a.Hout = g.Hout; a.Wout = g.Wout;  // geometry(): the windows' sizes
+  a.ncols = g.ncols;
+  a.ncb = g.ncb;
+  a.ncbu = g.ncbu;
+  a.J = g.J;
+  a.bl = d->bandlimit;
+  a.adjoint = d->adjoint;
+  a.dx = d->dx;
+  a.dy = d->dy;
+  a.scale = (float)(1.0 / ((double)g.Ph * (double)g.Pw));
+  for (int c = 0; c < d->C; ++c) a.lam[c] = d->wavelengths[c];
+  if (d->z)
+    for (int zi = 0; zi < d->Z; ++zi) a.zv[zi] = d->z[zi];
+  a.zdev = d->z_dev;
+  return a;
+}
+
 // Compile-time power-of-two instantiations (blockDim = n / FFT_MAXV); 0 = runtime plan.
 static int pow2_kind(int n) {
   switch (n) {
@@ -1720,6 +1685,19 @@ static int threads_for(int n) { return pow2_kind(n) ? n / pow2_v(n) : fft_thread
     case 16384: hipLaunchKernelGGL(KER<16384>, __VA_ARGS__); break;                                \
     default: hipLaunchKernelGGL(KER<0>, __VA_ARGS__); break;                                       \
   }
+// kernels that exist for the compile-time power-of-two sizes only (the z-x slice column passes;
+// validate_slice has refused every other n)
+#define THZ_POW2_ONLY_SWITCH(n, KER, ...)                                                         \
+  switch (n) {                                                                                     \
+    case 1024: hipLaunchKernelGGL(KER<1024>, __VA_ARGS__); break;                                  \
+    case 2048: hipLaunchKernelGGL(KER<2048>, __VA_ARGS__); break;                                  \
+    case 4096: hipLaunchKernelGGL(KER<4096>, __VA_ARGS__); break;                                  \
+    case 8192: hipLaunchKernelGGL(KER<8192>, __VA_ARGS__); break;                                  \
+    default: hipLaunchKernelGGL(KER<16384>, __VA_ARGS__); break;                                   \
+  }
+
+// dynamic LDS of the power-of-two column passes: the transform, then mz, zok and the z values (ColLds)
+static size_t k2_lds_bytes(int Ph) { return fft_lds_bytes(Ph) + 12 * THZ_MAX_Z; }
 
 template <int PN>
 static void add_kernels(std::vector<const void*>& ks) {
@@ -1737,6 +1715,7 @@ static void add_kernels(std::vector<const void*>& ks) {
 template <int PN>
 static void add_slice_kernels(std::vector<const void*>& ks) {
   ks.push_back((const void*)asm_cols_slice<PN>);
+  ks.push_back((const void*)asm_cols_slice_adj<PN>);
   ks.push_back((const void*)asm_rows_slice<PN>);
 }
 
@@ -1745,7 +1724,7 @@ static int ensure_lds_attr() {
   static std::once_flag once;
   static hipError_t err = hipSuccess;
   std::call_once(once, [] {
-    const int mx = (int)fft_lds_bytes(FFT_MAX_N) + 12 * THZ_MAX_Z;
+    const int mx = (int)k2_lds_bytes(FFT_MAX_N);
     std::vector<const void*> ks;
     add_kernels<0>(ks);
     add_kernels<1024>(ks);
@@ -1759,11 +1738,6 @@ static int ensure_lds_attr() {
     add_slice_kernels<8192>(ks);
     add_slice_kernels<16384>(ks);
     ks.push_back((const void*)asm_rows_slice<0>);
-    ks.push_back((const void*)asm_cols_slice_adj<1024>);
-    ks.push_back((const void*)asm_cols_slice_adj<2048>);
-    ks.push_back((const void*)asm_cols_slice_adj<4096>);
-    ks.push_back((const void*)asm_cols_slice_adj<8192>);
-    ks.push_back((const void*)asm_cols_slice_adj<16384>);
     for (const void* k : ks) {
       hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
       if (e != hipSuccess) err = e;
@@ -1975,7 +1949,7 @@ static int run_pipeline(AsmArgs a, const AsmGeom& g, int Z, const void* in, void
         else
           THZ_MX_COLS(g.Ph, asm_cols_mx, dim3(ntask), dim3(mx_threads(g.Ph)), lds2, s, (const float2*)T, U, ph, a);
       } else {
-        const size_t lds2 = fft_lds_bytes(g.Ph) + 12 * THZ_MAX_Z;  // mz, zok and the z values
+        const size_t lds2 = k2_lds_bytes(g.Ph);
         const int ntask = k2_tasks(g, &a, th, lds2);
         a.zrec = !plane_recurrence_disabled();
         THZ_POW2_SWITCH(g.Ph, asm_cols, dim3(ntask), dim3(th), lds2, s, (const float2*)T, U, ph, a);
@@ -2013,16 +1987,6 @@ static int run_pipeline(AsmArgs a, const AsmGeom& g, int Z, const void* in, void
   return THZ_OK;
 }
 
-// the z-x slice kernels: the column pass exists for the compile-time power-of-two heights only
-#define THZ_SLICE_COLS(n, ...)                                                                     \
-  switch (n) {                                                                                     \
-    case 1024: hipLaunchKernelGGL(asm_cols_slice<1024>, __VA_ARGS__); break;                       \
-    case 2048: hipLaunchKernelGGL(asm_cols_slice<2048>, __VA_ARGS__); break;                       \
-    case 4096: hipLaunchKernelGGL(asm_cols_slice<4096>, __VA_ARGS__); break;                       \
-    case 8192: hipLaunchKernelGGL(asm_cols_slice<8192>, __VA_ARGS__); break;                       \
-    default: hipLaunchKernelGGL(asm_cols_slice<16384>, __VA_ARGS__); break;                        \
-  }
-
 // planes per cols_slice launch: the full path's z-chunk (so the recurrence starts where it does
 // there), at most SLICE_ZC
 static int slice_zc(const AsmGeom& g) { return std::min(g.zc, SLICE_ZC); }
@@ -2046,7 +2010,7 @@ static int run_slice(AsmArgs a, const AsmGeom& g, int Z, int R, const void* in, 
     THZ_LAUNCH_CHECK();
     kt.stop();
   }
-  const size_t lds2 = fft_lds_bytes(g.Ph) + 12 * THZ_MAX_Z;  // mz, zok and the z values, as asm_cols
+  const size_t lds2 = k2_lds_bytes(g.Ph);
   a.zrec = !plane_recurrence_disabled();
   for (int z0 = 0; z0 < Z; z0 += zc) {
     a.zoff = z0;
@@ -2054,7 +2018,7 @@ static int run_slice(AsmArgs a, const AsmGeom& g, int Z, int R, const void* in, 
     {
       KernelTimer kt("asm_cols_slice", s);
       const int ntask = k2_tasks(g, &a, th, lds2);  // asm_cols' own task split
-      THZ_SLICE_COLS(g.Ph, dim3(ntask), dim3(th), lds2, s, (const float2*)T, V, ph, a, R);
+      THZ_POW2_ONLY_SWITCH(g.Ph, asm_cols_slice, dim3(ntask), dim3(th), lds2, s, (const float2*)T, V, ph, a, R);
       THZ_LAUNCH_CHECK();
       kt.stop();
     }
@@ -2068,15 +2032,6 @@ static int run_slice(AsmArgs a, const AsmGeom& g, int Z, int R, const void* in, 
   }
   return THZ_OK;
 }
-
-#define THZ_SLICE_ADJ_COLS(n, ...)                                                                 \
-  switch (n) {                                                                                     \
-    case 1024: hipLaunchKernelGGL(asm_cols_slice_adj<1024>, __VA_ARGS__); break;                   \
-    case 2048: hipLaunchKernelGGL(asm_cols_slice_adj<2048>, __VA_ARGS__); break;                   \
-    case 4096: hipLaunchKernelGGL(asm_cols_slice_adj<4096>, __VA_ARGS__); break;                   \
-    case 8192: hipLaunchKernelGGL(asm_cols_slice_adj<8192>, __VA_ARGS__); break;                   \
-    default: hipLaunchKernelGGL(asm_cols_slice_adj<16384>, __VA_ARGS__); break;                    \
-  }
 
 // the slice adjoint's workspace (g: the geometry of the adjoint descriptor, Hout x Wout the field):
 // the gradient spectrum U of one plane, in the layout asm_rows_inv reads, and Gv [Z][BC][ncb CB]
@@ -2107,9 +2062,10 @@ static int run_slice_adjoint(AsmArgs a, const AsmGeom& g, int Z, int R, const vo
   }
   {
     KernelTimer kt("asm_cols_slice_adj", s);
-    const size_t lds2 = fft_lds_bytes(g.Ph) + 12 * THZ_MAX_Z;  // mz, zok and the z values, as asm_cols_slice
+    const size_t lds2 = k2_lds_bytes(g.Ph);
     a.zrec = !plane_recurrence_disabled();
-    THZ_SLICE_ADJ_COLS(g.Ph, dim3(g.ncols * g.BC), dim3(threads_for(g.Ph)), lds2, s, (const float2*)Gv, U, ph, a, R);
+    THZ_POW2_ONLY_SWITCH(g.Ph, asm_cols_slice_adj, dim3(g.ncols * g.BC), dim3(threads_for(g.Ph)), lds2, s,
+                         (const float2*)Gv, U, ph, a, R);
     THZ_LAUNCH_CHECK();
     kt.stop();
   }
@@ -2169,23 +2125,7 @@ extern "C" int thz_asm_slice_forward(const thz_asm_desc* d, int row, const void*
   FftPlan pw, ph;
   if ((e = get_plan(g.Pw, &pw))) return e;
   if ((e = get_plan(g.Ph, &ph))) return e;
-  AsmArgs a{};
-  a.BC = g.BC;
-  a.C = d->C;
-  a.Ph = g.Ph;
-  a.Pw = g.Pw;
-  a.in_r0 = d->pad_h; a.in_c0 = d->pad_w; a.Hin = d->H; a.Win = d->W;
-  a.out_r0 = d->unpad ? d->pad_h : 0; a.out_c0 = d->unpad ? d->pad_w : 0; a.Hout = g.Hout; a.Wout = g.Wout;
-  a.ncols = g.ncols;
-  a.ncb = g.ncb;
-  a.ncbu = g.ncbu;
-  a.J = g.J;
-  a.bl = d->bandlimit;
-  a.dx = d->dx;
-  a.dy = d->dy;
-  a.scale = (float)(1.0 / ((double)g.Ph * (double)g.Pw));
-  for (int c = 0; c < d->C; ++c) a.lam[c] = d->wavelengths[c];
-  for (int zi = 0; zi < d->Z; ++zi) a.zv[zi] = d->z[zi];
+  const AsmArgs a = asm_args_base(d, g);
   float2* T = (float2*)workspace;
   float2* V = (float2*)((char*)workspace + t_bytes(g));
   return run_slice(a, g, d->Z, row + a.out_r0, in, out, T, V, (hipStream_t)stream, pw, ph);
@@ -2215,24 +2155,7 @@ extern "C" int thz_asm_slice_adjoint(const thz_asm_desc* d, int row, const void*
   FftPlan pw, ph;
   if ((e = get_plan(g.Pw, &pw))) return e;
   if ((e = get_plan(g.Ph, &ph))) return e;
-  AsmArgs a{};
-  a.BC = g.BC;
-  a.C = d->C;
-  a.Ph = g.Ph;
-  a.Pw = g.Pw;
-  a.in_r0 = d->unpad ? d->pad_h : 0; a.in_c0 = d->unpad ? d->pad_w : 0; a.Hin = g.Hin; a.Win = g.Win;
-  a.out_r0 = d->pad_h; a.out_c0 = d->pad_w; a.Hout = g.Hout; a.Wout = g.Wout;
-  a.ncols = g.ncols;
-  a.ncb = g.ncb;
-  a.ncbu = g.ncbu;
-  a.J = g.J;
-  a.bl = d->bandlimit;
-  a.adjoint = 1;
-  a.dx = d->dx;
-  a.dy = d->dy;
-  a.scale = (float)(1.0 / ((double)g.Ph * (double)g.Pw));
-  for (int c = 0; c < d->C; ++c) a.lam[c] = d->wavelengths[c];
-  for (int zi = 0; zi < d->Z; ++zi) a.zv[zi] = d->z[zi];
+  const AsmArgs a = asm_args_base(d, g);
   float2* U = (float2*)workspace;
   float2* Gv = (float2*)((char*)workspace + slice_adj_u_bytes(g));
   return run_slice_adjoint(a, g, d->Z, row + a.in_r0, grad_out, grad_in, U, Gv, (hipStream_t)stream, pw, ph);
@@ -2276,33 +2199,7 @@ static int asm_forward_impl(const thz_asm_desc* d, const thz_doe_desc* m, const 
   if ((e = get_plan(g.Pw, &pw))) return e;
   if ((e = get_plan(g.Ph, &ph))) return e;
 
-  AsmArgs a{};
-  a.BC = g.BC;
-  a.C = d->C;
-  a.Ph = g.Ph;
-  a.Pw = g.Pw;
-  const int Ho = d->unpad ? d->H : g.Ph, Wo = d->unpad ? d->W : g.Pw;
-  const int o_r0 = d->unpad ? d->pad_h : 0, o_c0 = d->unpad ? d->pad_w : 0;
-  if (!d->adjoint) {
-    a.in_r0 = d->pad_h; a.in_c0 = d->pad_w; a.Hin = d->H; a.Win = d->W;
-    a.out_r0 = o_r0; a.out_c0 = o_c0; a.Hout = Ho; a.Wout = Wo;
-  } else {
-    a.in_r0 = o_r0; a.in_c0 = o_c0; a.Hin = Ho; a.Win = Wo;
-    a.out_r0 = d->pad_h; a.out_c0 = d->pad_w; a.Hout = d->H; a.Wout = d->W;
-  }
-  a.ncols = g.ncols;
-  a.ncb = g.ncb;
-  a.ncbu = g.ncbu;
-  a.J = g.J;
-  a.bl = d->bandlimit;
-  a.adjoint = d->adjoint;
-  a.dx = d->dx;
-  a.dy = d->dy;
-  a.scale = (float)(1.0 / ((double)g.Ph * (double)g.Pw));
-  for (int c = 0; c < d->C; ++c) a.lam[c] = d->wavelengths[c];
-  if (d->z)
-    for (int zi = 0; zi < d->Z; ++zi) a.zv[zi] = d->z[zi];
-  a.zdev = d->z_dev;
+  AsmArgs a = asm_args_base(d, g);
   if (m) {
     a.mod_h = mh;
     a.mod_u = mu;
@@ -2317,6 +2214,7 @@ static int asm_forward_impl(const thz_asm_desc* d, const thz_doe_desc* m, const 
   }
   if (d->window_mask) {
     const thz_aperture_desc* w = d->window_mask;
+    const int Ho = d->adjoint ? g.Hin : g.Hout, Wo = d->adjoint ? g.Win : g.Wout;  // the forward's output grid
     if (w->kind != THZ_APERTURE_RECT && w->kind != THZ_APERTURE_CIRC)
       return fail(THZ_E_ARG, "window mask: bad aperture kind %d", w->kind);
     if (w->H != Ho || w->W != Wo)
