@@ -1639,105 +1639,119 @@ static void geometry(const thz_asm_desc* d, AsmGeom* g) {
   g->adj = d->adjoint;
 }
 
-// The argument block as every ASM entry point starts it: sizes, the forward's windows or
-// (d->adjoint) the adjoint's, the band, spacings, scale, wavelengths and the planes.
-static AsmArgs asm_args_base(const thz_asm_desc* d, const AsmGeom& g) {
+// The argument block every pipeline on this file starts from: the sizes and window sizes of the
+// geometry, the band, the spacings, the transform's 1 / (Ph Pw) and the wavelengths.  The callers
+// add what is theirs: the windows' origins, the direction and the planes.
+static AsmArgs args_base(const AsmGeom& g, int bandlimit, float dx, float dy, const float* wavelengths) {
   AsmArgs a{};
   a.BC = g.BC;
-  a.C = d->C;
+  a.C = g.C;
   a.Ph = g.Ph;
   a.Pw = g.Pw;
-  const int o_r0 = d->unpad ? d->pad_h : 0, o_c0 = d->unpad ? d->pad_w : 0;
-  a.in_r0 = d->adjoint ? o_r0 : d->pad_h; a.in_c0 = d->adjoint ? o_c0 : d->pad_w;
-  a.out_r0 = d->adjoint ? d->pad_h : o_r0; a.out_c0 = d->adjoint ? d->pad_w : o_c0;
   a.Hin = g.Hin; a.Win = g.Win; a.Hout = g.Hout; a.Wout = g.Wout;  // geometry(): the windows' sizes
   a.ncols = g.ncols;
   a.ncb = g.ncb;
   a.ncbu = g.ncbu;
   a.J = g.J;
-  a.bl = d->bandlimit;
-  a.adjoint = d->adjoint;
-  a.dx = d->dx;
-  a.dy = d->dy;
+  a.bl = bandlimit;
+  a.dx = dx;
+  a.dy = dy;
   a.scale = (float)(1.0 / ((double)g.Ph * (double)g.Pw));
-  for (int c = 0; c < d->C; ++c) a.lam[c] = d->wavelengths[c];
+  for (int c = 0; c < g.C; ++c) a.lam[c] = wavelengths[c];
+  return a;
+}
+
+// The argument block as every ASM entry point starts it: the base, the forward's windows or
+// (d->adjoint) the adjoint's, and the planes.
+static AsmArgs asm_args_base(const thz_asm_desc* d, const AsmGeom& g) {
+  AsmArgs a = args_base(g, d->bandlimit, d->dx, d->dy, d->wavelengths);
+  const int o_r0 = d->unpad ? d->pad_h : 0, o_c0 = d->unpad ? d->pad_w : 0;
+  a.in_r0 = d->adjoint ? o_r0 : d->pad_h; a.in_c0 = d->adjoint ? o_c0 : d->pad_w;
+  a.out_r0 = d->adjoint ? d->pad_h : o_r0; a.out_c0 = d->adjoint ? d->pad_w : o_c0;
+  a.adjoint = d->adjoint;
   if (d->z)
     for (int zi = 0; zi < d->Z; ++zi) a.zv[zi] = d->z[zi];
   a.zdev = d->z_dev;
   return a;
 }
 
-// Compile-time power-of-two instantiations (blockDim = n / FFT_MAXV); 0 = runtime plan.
-static int pow2_kind(int n) {
-  switch (n) {
-    case 1024: case 2048: case 4096: case 8192: case 16384: return n;
-    default: return 0;
-  }
+// ---- the instantiated sizes ------------------------------------------------------------------
+// The one list of compile-time power-of-two transform lengths (blockDim = n / FFT_MAXV); the
+// mixed-radix lengths are Mx300 / Mx500 (is_mx, MxOf) and every other length runs the runtime plan
+// (the <0> instantiation).  A dispatcher calls f(Size<N>{}) for the instantiation that serves n,
+// so `KER<N()>` inside a generic lambda names the kernel; one dispatcher per kind of kernel family.
+template <int N>
+using Size = std::integral_constant<int, N>;
+template <int... Ns>
+struct SizeList {};
+using Pow2Sizes = SizeList<1024, 2048, 4096, 8192, 16384>;
+
+template <class F, int... Ns>
+static bool on_listed(SizeList<Ns...>, int n, F&& f) {
+  return ((n == Ns ? (f(Size<Ns>{}), true) : false) || ...);
 }
+template <class F, int... Ns>
+static void for_each_size(SizeList<Ns...>, F&& f) {
+  (f(Size<Ns>{}), ...);
+}
+// families that exist for the compile-time powers of two only (the z-x slice column passes):
+// false when n is none of them
+template <class F>
+static bool on_pow2_only(int n, F&& f) {
+  return on_listed(Pow2Sizes{}, n, f);
+}
+// families with a runtime-plan instantiation behind the powers of two (asm_cols, asm_rows_slice,
+// fft_rows_kernel, the RSC kernel transforms)
+template <class F>
+static void on_pow2(int n, F&& f) {
+  if (!on_listed(Pow2Sizes{}, n, f)) f(Size<0>{});
+}
+// the row passes K1 / K3: the mixed-radix instantiations, then as on_pow2
+template <class F>
+static void on_rows(int n, F&& f) {
+  if (!on_listed(SizeList<Mx300::N, Mx500::N>{}, n, f)) on_pow2(n, f);
+}
+// the mixed-radix column pass and its tables, templated on the plan: f(Mx300{}) or f(Mx500{})
+template <class F>
+static void on_mx(int n, F&& f) {
+  if (n == Mx300::N) f(Mx300{});
+  else f(Mx500{});
+}
+
+static int pow2_kind(int n) { return on_pow2_only(n, [](auto) {}) ? n : 0; }
+// workgroup sizes: the power-of-two / runtime-plan families, and the row passes (which have the
+// mixed-radix instantiations before those)
 static int threads_for(int n) { return pow2_kind(n) ? n / pow2_v(n) : fft_threads(n); }
+static int rows_threads(int n) { return is_mx(n) ? mx_threads(n) : threads_for(n); }
 
-#define THZ_POW2_SWITCH(n, KER, ...)                                                              \
-  switch (pow2_kind(n)) {                                                                          \
-    case 1024: hipLaunchKernelGGL(KER<1024>, __VA_ARGS__); break;                                  \
-    case 2048: hipLaunchKernelGGL(KER<2048>, __VA_ARGS__); break;                                  \
-    case 4096: hipLaunchKernelGGL(KER<4096>, __VA_ARGS__); break;                                  \
-    case 8192: hipLaunchKernelGGL(KER<8192>, __VA_ARGS__); break;                                  \
-    case 16384: hipLaunchKernelGGL(KER<16384>, __VA_ARGS__); break;                                \
-    default: hipLaunchKernelGGL(KER<0>, __VA_ARGS__); break;                                       \
-  }
-// kernels that exist for the compile-time power-of-two sizes only (the z-x slice column passes;
-// validate_slice has refused every other n)
-#define THZ_POW2_ONLY_SWITCH(n, KER, ...)                                                         \
-  switch (n) {                                                                                     \
-    case 1024: hipLaunchKernelGGL(KER<1024>, __VA_ARGS__); break;                                  \
-    case 2048: hipLaunchKernelGGL(KER<2048>, __VA_ARGS__); break;                                  \
-    case 4096: hipLaunchKernelGGL(KER<4096>, __VA_ARGS__); break;                                  \
-    case 8192: hipLaunchKernelGGL(KER<8192>, __VA_ARGS__); break;                                  \
-    default: hipLaunchKernelGGL(KER<16384>, __VA_ARGS__); break;                                   \
-  }
-
-// dynamic LDS of the power-of-two column passes: the transform, then mz, zok and the z values (ColLds)
+// Dynamic LDS of the column passes, one definition per kernel family.  Power of two and runtime
+// plan: the transform, then mz, zok and the z values (ColLds); their Z-summing form keeps mz only;
+// the mixed-radix kernels hold the data rows (their twiddles live in registers) and mz.
 static size_t k2_lds_bytes(int Ph) { return fft_lds_bytes(Ph) + 12 * THZ_MAX_Z; }
+static size_t k2_zsum_lds_bytes(int Ph) { return fft_lds_bytes(Ph) + 4 * THZ_MAX_Z; }
+static size_t k2_mx_lds_bytes(int Ph) { return lds_floats2(Ph) * sizeof(float2) + 4 * THZ_MAX_Z; }
 
-template <int PN>
-static void add_kernels(std::vector<const void*>& ks) {
-  ks.push_back((const void*)asm_rows_fwd<PN>);
-  ks.push_back((const void*)asm_cols<PN>);
-  if constexpr (PN == 8192) ks.push_back((const void*)asm_rows_inv_mid<PN>);
-  ks.push_back((const void*)asm_cols_zsum<PN>);
-  ks.push_back((const void*)asm_rows_inv<PN>);
-  ks.push_back((const void*)asm_rows_inv_loss<PN>);
-  ks.push_back((const void*)fft_rows_kernel<PN>);
-  ks.push_back((const void*)rsc_k_rows<PN>);
-  ks.push_back((const void*)rsc_k_cols<PN>);
-}
-
-template <int PN>
-static void add_slice_kernels(std::vector<const void*>& ks) {
-  ks.push_back((const void*)asm_cols_slice<PN>);
-  ks.push_back((const void*)asm_cols_slice_adj<PN>);
-  ks.push_back((const void*)asm_rows_slice<PN>);
-}
-
-// Workgroups above 64 KiB of dynamic LDS must opt in once per kernel.
+// Workgroups above 64 KiB of dynamic LDS must opt in once per kernel: every kernel of the
+// power-of-two and runtime-plan sizes (the mixed-radix ones stay far below).
 static int ensure_lds_attr() {
   static std::once_flag once;
   static hipError_t err = hipSuccess;
   std::call_once(once, [] {
     const int mx = (int)k2_lds_bytes(FFT_MAX_N);
     std::vector<const void*> ks;
-    add_kernels<0>(ks);
-    add_kernels<1024>(ks);
-    add_kernels<2048>(ks);
-    add_kernels<4096>(ks);
-    add_kernels<8192>(ks);
-    add_kernels<16384>(ks);
-    add_slice_kernels<1024>(ks);
-    add_slice_kernels<2048>(ks);
-    add_slice_kernels<4096>(ks);
-    add_slice_kernels<8192>(ks);
-    add_slice_kernels<16384>(ks);
-    ks.push_back((const void*)asm_rows_slice<0>);
+    auto planes = [&](auto N) {
+      constexpr int PN = N();
+      ks.insert(ks.end(), {(const void*)asm_rows_fwd<PN>, (const void*)asm_cols<PN>, (const void*)asm_cols_zsum<PN>,
+                           (const void*)asm_rows_inv<PN>, (const void*)asm_rows_inv_loss<PN>,
+                           (const void*)asm_rows_slice<PN>, (const void*)fft_rows_kernel<PN>,
+                           (const void*)rsc_k_rows<PN>, (const void*)rsc_k_cols<PN>});
+      if constexpr (PN == 8192) ks.push_back((const void*)asm_rows_inv_mid<PN>);
+    };
+    for_each_size(Pow2Sizes{}, planes);
+    planes(Size<0>{});
+    for_each_size(Pow2Sizes{}, [&](auto N) {
+      ks.insert(ks.end(), {(const void*)asm_cols_slice<N()>, (const void*)asm_cols_slice_adj<N()>});
+    });
     for (const void* k : ks) {
       hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
       if (e != hipSuccess) err = e;
@@ -1750,28 +1764,12 @@ static int ensure_lds_attr() {
 
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// Workgroups of the column pass resident on the whole device at once (CUs x occupancy).
-// Ph / Pw with a compile-time mixed-radix kernel (asm_cols_mx, asm_rows_*<N>), else 0
-static int mx_kind(int n) { return is_mx(n) ? n : 0; }
-// K1 / K3: the mixed-radix instantiation or the power-of-two switch
-#define THZ_ROWS_SWITCH(n, KER, G, LDSB, ...)                                                      \
-  if (mx_kind(n) == Mx300::N) hipLaunchKernelGGL(KER<Mx300::N>, G, dim3(MX_T), LDSB, __VA_ARGS__); \
-  else if (mx_kind(n) == Mx500::N) hipLaunchKernelGGL(KER<Mx500::N>, G, dim3(mx_threads(500)), LDSB, __VA_ARGS__); \
-  else THZ_POW2_SWITCH(n, KER, G, dim3(threads_for(n)), LDSB, __VA_ARGS__)
-// the mixed-radix column-pass kernels (asm_cols_mx*, templated on the plan) and their tables
-#define THZ_MX_COLS(n, KER, ...)                                                                   \
-  if ((n) == Mx300::N) hipLaunchKernelGGL(KER<Mx300>, __VA_ARGS__);                               \
-  else hipLaunchKernelGGL(KER<Mx500>, __VA_ARGS__)
-#define THZ_MX_TABLES(n, ...)                                                                      \
-  if ((n) == Mx300::N) hipLaunchKernelGGL(asm_tf_tables<Mx300::N>, __VA_ARGS__);                  \
-  else hipLaunchKernelGGL(asm_tf_tables<Mx500::N>, __VA_ARGS__)
-
 // The 300-point passes with the layers' windows ([N/3, 2N/3) in and out: padding 2 with unpad,
 // cfg4 / cfg5) as compile-time constants: the column pass (asm_cols_mx_mid: 80.8 vs 83.3 us per
 // launch, cfg5 chained 1.097 vs 1.133 ms), K1 (asm_rows_fwd<300, true>) and K3
 // (asm_rows_inv_mid<300>, asm_rows_inv_loss_mid<300>).  The A/B records: profiles/r04_experiments.txt.
-static bool mx_mid(const AsmArgs& a) {
-  return !a.tft && a.in_r0 == Mx300::N / 3 && a.Hin == Mx300::N / 3 && a.out_r0 == Mx300::N / 3 &&
+static bool mx_mid(int Ph, const AsmArgs& a) {
+  return Ph == Mx300::N && !a.tft && a.in_r0 == Mx300::N / 3 && a.Hin == Mx300::N / 3 && a.out_r0 == Mx300::N / 3 &&
          a.Hout == Mx300::N / 3;
 }
 // K3 with its crop as a compile-time window: the middle half of P = 8192 (asm_rows_inv_mid<8192>,
@@ -1782,6 +1780,19 @@ static bool k3_mid(int Pw, const AsmArgs& a) {
 }
 // K1 of the 300-point layers with the input window as constants (asm_rows_fwd<300, true>)
 static bool k1_mid(int Pw, const AsmArgs& a) { return Pw == Mx300::N && a.in_c0 == Pw / 3 && a.Win == Pw / 3; }
+
+// every row and column pass of the planes' pipelines has this signature
+using PassKernel = void (*)(const float2*, float2*, FftPlan, AsmArgs);
+
+// the column pass of the planes (asm_cols, or asm_cols_mx on a mixed-radix height)
+static PassKernel cols_kernel(int Ph) {
+  PassKernel k = nullptr;
+  if (is_mx(Ph)) on_mx(Ph, [&](auto P) { k = asm_cols_mx<decltype(P)>; });
+  else on_pow2(Ph, [&](auto N) { k = asm_cols<N()>; });
+  return k;
+}
+
+// Workgroups of the column pass resident on the whole device at once (CUs x occupancy).
 static int k2_resident(int Ph, int threads, size_t lds) {
   static std::mutex mu;
   static std::map<std::tuple<int, int, int, size_t>, int> cache;
@@ -1791,19 +1802,8 @@ static int k2_resident(int Ph, int threads, size_t lds) {
   auto key = std::make_tuple(dev, Ph, threads, lds);
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
-  const void* k = nullptr;
-  switch (pow2_kind(Ph)) {
-    case 1024: k = (const void*)asm_cols<1024>; break;
-    case 2048: k = (const void*)asm_cols<2048>; break;
-    case 4096: k = (const void*)asm_cols<4096>; break;
-    case 8192: k = (const void*)asm_cols<8192>; break;
-    case 16384: k = (const void*)asm_cols<16384>; break;
-    default: k = (const void*)asm_cols<0>; break;
-  }
-  if (mx_kind(Ph) == Mx300::N) k = (const void*)asm_cols_mx<Mx300>;
-  if (mx_kind(Ph) == Mx500::N) k = (const void*)asm_cols_mx<Mx500>;
   int per_cu = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, threads, lds) != hipSuccess ||
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)cols_kernel(Ph), threads, lds) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     per_cu = cus = 0;
   const int r = per_cu * cus;
@@ -1826,73 +1826,6 @@ static int k2_tasks(const AsmGeom& g, AsmArgs* a, int threads, size_t lds) {
   return full + rem * a->kparts;
 }
 
-// the mixed-radix column pass's per-(wavelength, column) tables, shared by every plane
-static size_t tab_sq_bytes(const AsmGeom& g) { return align256((size_t)g.C * g.ncols * g.Ph * sizeof(float)); }
-static size_t tab_bytes(const AsmGeom& g) {
-  return mx_kind(g.Ph) ? tab_sq_bytes(g) + align256((size_t)g.C * g.ncols * g.zc * sizeof(int)) : 0;
-}
-static size_t t_bytes(const AsmGeom& g) {
-  return align256((size_t)(g.adj ? g.zc : 1) * g.BC * g.ncb * CB * g.Hin * sizeof(float2));
-}
-static size_t ws_bytes(const AsmGeom& g) {
-  return t_bytes(g) + align256((size_t)(g.adj ? 1 : g.zc) * g.BC * g.ncbu * CBU * u_rows(g.Hout) * sizeof(float2)) +
-         tab_bytes(g);
-}
-
-// The adjoint of a Z-plane forward (sum over planes): per z-chunk, K1 over the chunk's input
-// planes and the Z-summing K2 (adding into U after the first chunk); then K3 once.
-static int run_adjoint_sum(AsmArgs a, const AsmGeom& g, int Z, const void* in, void* out, float2* T, float2* U,
-                           hipStream_t s, FftPlan pw, FftPlan ph, bool mx_tabs) {
-  a.zsum = 1;
-  a.tab_blocks = 0;
-  a.kfull = g.ncols * g.BC;  // every column task runs all of its chunk's planes
-  a.kparts = 1;
-  const int th = threads_for(g.Ph);
-  for (int z0 = 0; z0 < Z; z0 += g.zc) {
-    a.zoff = z0;
-    a.nz = std::min(g.zc, Z - z0);
-    a.zacc = z0 > 0;
-    {
-      KernelTimer kt("asm_rows_fwd", s);
-      if (k1_mid(g.Pw, a)) {
-        hipLaunchKernelGGL((asm_rows_fwd<Mx300::N, true>), dim3(a.nz * g.BC * g.Hin), dim3(MX_T), fft_lds_bytes_io(g.Pw),
-                           s, (const float2*)in, T, pw, a);
-      } else {
-        THZ_ROWS_SWITCH(g.Pw, asm_rows_fwd, dim3(a.nz * g.BC * g.Hin), fft_lds_bytes_io(g.Pw), s, (const float2*)in,
-                        T, pw, a);
-      }
-      THZ_LAUNCH_CHECK();
-      kt.stop();
-    }
-    {
-      KernelTimer kt("asm_cols", s);
-      if (mx_kind(g.Ph)) {
-        if (mx_tabs) {
-          THZ_MX_TABLES(g.Ph, dim3(g.C * g.ncols), dim3(MX_T), 0, s, a, z0 == 0);
-          THZ_LAUNCH_CHECK();
-        }
-        const size_t lds2 = lds_floats2(g.Ph) * sizeof(float2) + 4 * THZ_MAX_Z;
-        THZ_MX_COLS(g.Ph, asm_cols_mx_zsum, dim3(a.kfull), dim3(mx_threads(g.Ph)), lds2, s, (const float2*)T, U, ph, a);
-      } else {
-        const size_t lds2 = fft_lds_bytes(g.Ph) + 4 * THZ_MAX_Z;
-        THZ_POW2_SWITCH(g.Ph, asm_cols_zsum, dim3(a.kfull), dim3(th), lds2, s, (const float2*)T, U, ph, a);
-      }
-      THZ_LAUNCH_CHECK();
-      kt.stop();
-    }
-  }
-  a.zoff = 0;
-  a.nz = 1;
-  {
-    KernelTimer kt("asm_rows_inv", s);
-    THZ_ROWS_SWITCH(g.Pw, asm_rows_inv, dim3(g.BC * g.Hout), fft_lds_bytes_io(g.Pw), s, (const float2*)U,
-                    (float2*)out, pw, a);
-    THZ_LAUNCH_CHECK();
-    kt.stop();
-  }
-  return THZ_OK;
-}
-
 // THZ_K2_RECURRENCE=0 keeps the per-plane sincos everywhere (the A/B and parity tests compare the
 // two forms; read per call so a test can toggle it)
 static bool plane_recurrence_disabled() {
@@ -1900,188 +1833,254 @@ static bool plane_recurrence_disabled() {
   return v && v[0] == '0';
 }
 
-// K1 once, then (K2, K3) per z-chunk, on a prepared argument block.
-static int run_pipeline(AsmArgs a, const AsmGeom& g, int Z, const void* in, void* out, float2* T, float2* U,
-                        hipStream_t s, FftPlan pw, FftPlan ph, char* tabs = nullptr) {
-  int e;
-  if ((e = ensure_lds_attr())) return e;
-  const int th = threads_for(g.Ph);
-  const bool mx_tabs = mx_kind(g.Ph) && !a.tft;
-  if (mx_tabs) {
-    if (!tabs) return fail(THZ_E_WORKSPACE, "mixed-radix column tables need workspace");
-    a.sqt = (float*)tabs;
-    a.mzt = (int*)(tabs + tab_sq_bytes(g));
-  }
-  if (g.adj && Z > 1) return run_adjoint_sum(a, g, Z, in, out, T, U, s, pw, ph, mx_tabs);
-  // square 300-point grids (cfg4 / cfg5): the first z-chunk's column tables ride along with K1
-  // (tf_tables_body<PN> of K1's own size: Ph == Pw)
-  a.tab_blocks = mx_tabs && g.Pw == g.Ph && g.Pw == Mx300::N ? g.C * g.ncols : 0;
-  {
-    KernelTimer kt("asm_rows_fwd", s);
-    a.zoff = 0;
-    a.nz = std::min(g.zc, Z);
-    if (k1_mid(g.Pw, a)) {
-      hipLaunchKernelGGL((asm_rows_fwd<Mx300::N, true>), dim3(g.BC * g.Hin + a.tab_blocks), dim3(MX_T),
-                         fft_lds_bytes_io(g.Pw), s, (const float2*)in, T, pw, a);
-    } else {
-      THZ_ROWS_SWITCH(g.Pw, asm_rows_fwd, dim3(g.BC * g.Hin + a.tab_blocks), fft_lds_bytes_io(g.Pw), s,
-                      (const float2*)in, T, pw, a);
-    }
-    THZ_LAUNCH_CHECK();
-    kt.stop();
-  }
-  for (int z0 = 0; z0 < Z; z0 += g.zc) {
-    a.zoff = z0;
-    a.nz = std::min(g.zc, Z - z0);
-    {
-      KernelTimer kt("asm_cols", s);
-      if (mx_kind(g.Ph)) {
-        if (mx_tabs && !(z0 == 0 && a.tab_blocks)) {
-          THZ_MX_TABLES(g.Ph, dim3(g.C * g.ncols), dim3(MX_T), 0, s, a, z0 == 0);
-          THZ_LAUNCH_CHECK();
-        }
-      }
-      if (mx_kind(g.Ph)) {
-        const size_t lds2 = lds_floats2(g.Ph) * sizeof(float2) + 4 * THZ_MAX_Z;
-        const int ntask = k2_tasks(g, &a, mx_threads(g.Ph), lds2);
-        if (g.Ph == Mx300::N && mx_mid(a))
-          hipLaunchKernelGGL(asm_cols_mx_mid<Mx300>, dim3(ntask), dim3(MX_T), lds2, s, (const float2*)T, U, ph, a);
-        else
-          THZ_MX_COLS(g.Ph, asm_cols_mx, dim3(ntask), dim3(mx_threads(g.Ph)), lds2, s, (const float2*)T, U, ph, a);
-      } else {
-        const size_t lds2 = k2_lds_bytes(g.Ph);
-        const int ntask = k2_tasks(g, &a, th, lds2);
-        a.zrec = !plane_recurrence_disabled();
-        THZ_POW2_SWITCH(g.Ph, asm_cols, dim3(ntask), dim3(th), lds2, s, (const float2*)T, U, ph, a);
-      }
-      THZ_LAUNCH_CHECK();
-      kt.stop();
-    }
-    {
-      KernelTimer kt("asm_rows_inv", s);
-      if (a.ls.stats) {
-        if (g.Pw == Mx300::N && k3_mid(g.Pw, a)) {
-          hipLaunchKernelGGL(asm_rows_inv_loss_mid<Mx300::N>, dim3(a.nz * g.BC * g.Hout), dim3(MX_T),
-                             fft_lds_bytes_io(g.Pw), s, (const float2*)U, (float2*)out, pw, a);
-        } else {
-          THZ_ROWS_SWITCH(g.Pw, asm_rows_inv_loss, dim3(a.nz * g.BC * g.Hout), fft_lds_bytes_io(g.Pw), s,
-                          (const float2*)U, (float2*)out, pw, a);
-        }
-        THZ_LAUNCH_CHECK();
-        if ((e = launch_loss_finish(a.ls, s))) return e;
-      } else if (k3_mid(g.Pw, a)) {
-        if (g.Pw == 8192)
-          hipLaunchKernelGGL(asm_rows_inv_mid<8192>, dim3(a.nz * g.BC * g.Hout), dim3(threads_for(8192)),
-                             fft_lds_bytes_io(8192), s, (const float2*)U, (float2*)out, pw, a);
-        else
-          hipLaunchKernelGGL(asm_rows_inv_mid<Mx300::N>, dim3(a.nz * g.BC * g.Hout), dim3(MX_T),
-                             fft_lds_bytes_io(g.Pw), s, (const float2*)U, (float2*)out, pw, a);
-      } else {
-        THZ_ROWS_SWITCH(g.Pw, asm_rows_inv, dim3(a.nz * g.BC * g.Hout), fft_lds_bytes_io(g.Pw), s, (const float2*)U,
-                        (float2*)out, pw, a);
-      }
-      THZ_LAUNCH_CHECK();
-      kt.stop();
-    }
-  }
-  return THZ_OK;
+// ---- workspace layouts -----------------------------------------------------------------------
+// T: K1's band spectra, one plane (the Z-summing adjoint: the z-chunk's planes)
+static size_t t_bytes(const AsmGeom& g) {
+  return align256((size_t)(g.adj ? g.zc : 1) * g.BC * g.ncb * CB * g.Hin * sizeof(float2));
 }
-
+// U: `planes` planes of column-pass output in the layout K3 gathers
+static size_t u_bytes(const AsmGeom& g, int planes) {
+  return align256((size_t)planes * g.BC * g.ncbu * CBU * u_rows(g.Hout) * sizeof(float2));
+}
+// the mixed-radix column pass's per-(wavelength, column) tables, shared by every plane: sqt, then mzt
+static size_t tab_sq_bytes(const AsmGeom& g) { return align256((size_t)g.C * g.ncols * g.Ph * sizeof(float)); }
+static size_t tab_bytes(const AsmGeom& g) {
+  return is_mx(g.Ph) ? tab_sq_bytes(g) + align256((size_t)g.C * g.ncols * g.zc * sizeof(int)) : 0;
+}
 // planes per cols_slice launch: the full path's z-chunk (so the recurrence starts where it does
 // there), at most SLICE_ZC
 static int slice_zc(const AsmGeom& g) { return std::min(g.zc, SLICE_ZC); }
-static size_t slice_v_bytes(const AsmGeom& g) {
-  return align256((size_t)slice_zc(g) * g.BC * g.ncols * sizeof(float2));  // V [zc][BC][ncols]
+
+// Which pipeline an entry point runs: it decides the validation and the workspace layout.
+enum class Pipe { Planes, Slice, SliceAdjoint };
+
+// A pipeline's workspace, part by part in address order.  The *_workspace_size entries return the
+// sum and asm_plan() cuts the caller's workspace by the same parts.
+struct WsLayout {
+  size_t part[3];
+  size_t total() const { return part[0] + part[1] + part[2]; }
+};
+static WsLayout ws_layout(Pipe pipe, const AsmGeom& g, int Z) {
+  switch (pipe) {
+    case Pipe::Slice:  // T | V [zc][BC][ncols]
+      return {{t_bytes(g), align256((size_t)slice_zc(g) * g.BC * g.ncols * sizeof(float2)), 0}};
+    case Pipe::SliceAdjoint:  // (g: the adjoint descriptor's, Hout x Wout the field) U of one plane | Gv [Z][BC][ncb CB]
+      return {{u_bytes(g, 1), align256((size_t)Z * g.BC * g.ncb * CB * sizeof(float2)), 0}};
+    default:  // T | U of a z-chunk (the Z-summing adjoint: one plane) | the mixed-radix tables
+      return {{t_bytes(g), u_bytes(g, g.adj ? 1 : g.zc), tab_bytes(g)}};
+  }
 }
-static size_t slice_ws_bytes(const AsmGeom& g) { return t_bytes(g) + slice_v_bytes(g); }
+
+static int check_workspace(const void* workspace, size_t bytes, size_t need) {
+  if (!workspace || bytes < need) return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", bytes, need);
+  return THZ_OK;
+}
+
+// what a call needs of the device before its first launch: the FFT plans of both axes and the
+// kernels' large-LDS opt-in
+static int device_plans(const AsmGeom& g, FftPlan* pw, FftPlan* ph) {
+  int e;
+  if ((e = get_plan(g.Pw, pw)) || (e = get_plan(g.Ph, ph))) return e;
+  return ensure_lds_attr();
+}
+
+// ---- the launch plan -------------------------------------------------------------------------
+// One call's launch plan: what the stage launchers need besides the z-chunk's argument block.
+struct AsmPlan {
+  AsmGeom g;
+  FftPlan pw, ph;
+  AsmArgs a;     // as the entry prepared it; the run_* loops work on a copy
+  hipStream_t s;
+  int Z;
+  char* ws[3];   // the workspace parts of ws_layout (nullptr: an empty part)
+};
+
+// K1 over `planes` input planes of a.Hin rows.  a.tab_blocks further workgroups compute the first
+// z-chunk's column tables (run_pipeline).
+static int launch_k1(const AsmPlan& p, const AsmArgs& a, int planes, const void* in, float2* T) {
+  const int Pw = p.g.Pw;
+  PassKernel k = nullptr;
+  if (k1_mid(Pw, a)) k = asm_rows_fwd<Mx300::N, true>;
+  else on_rows(Pw, [&](auto N) { k = asm_rows_fwd<N()>; });
+  KernelTimer kt("asm_rows_fwd", p.s);
+  hipLaunchKernelGGL(k, dim3(planes * a.BC * a.Hin + a.tab_blocks), dim3(rows_threads(Pw)), fft_lds_bytes_io(Pw), p.s,
+                     (const float2*)in, T, p.pw, a);
+  THZ_LAUNCH_CHECK();
+  kt.stop();
+  return THZ_OK;
+}
+
+// The column pass of the z-chunk [a.zoff, a.zoff + a.nz): the planes' (split into k2_tasks) or, with
+// a.zsum, the Z-summing adjoint's (every column task runs all of its chunk's planes).  `tables`: the
+// mixed-radix tables of this chunk first, inside the same timer bracket.
+static int launch_cols(const AsmPlan& p, AsmArgs& a, bool tables, const float2* T, float2* U) {
+  const AsmGeom& g = p.g;
+  const bool mx = is_mx(g.Ph);
+  const int th = mx ? mx_threads(g.Ph) : threads_for(g.Ph);
+  const size_t lds = mx ? k2_mx_lds_bytes(g.Ph) : a.zsum ? k2_zsum_lds_bytes(g.Ph) : k2_lds_bytes(g.Ph);
+  PassKernel k = nullptr;
+  if (a.zsum) {
+    if (mx) on_mx(g.Ph, [&](auto P) { k = asm_cols_mx_zsum<decltype(P)>; });
+    else on_pow2(g.Ph, [&](auto N) { k = asm_cols_zsum<N()>; });
+  } else {
+    k = mx_mid(g.Ph, a) ? asm_cols_mx_mid<Mx300> : cols_kernel(g.Ph);
+  }
+  KernelTimer kt("asm_cols", p.s);
+  if (tables) {
+    on_mx(g.Ph, [&](auto P) {
+      hipLaunchKernelGGL(asm_tf_tables<decltype(P)::N>, dim3(g.C * g.ncols), dim3(MX_T), 0, p.s, a, a.zoff == 0);
+    });
+    THZ_LAUNCH_CHECK();
+  }
+  int ntask = g.ncols * g.BC;
+  if (a.zsum) {
+    a.kfull = ntask;
+    a.kparts = 1;
+  } else {
+    ntask = k2_tasks(g, &a, th, lds);
+    if (!mx) a.zrec = !plane_recurrence_disabled();
+  }
+  hipLaunchKernelGGL(k, dim3(ntask), dim3(th), lds, p.s, T, U, p.ph, a);
+  THZ_LAUNCH_CHECK();
+  kt.stop();
+  return THZ_OK;
+}
+
+// K3 over the a.nz planes in U: plain, or with the loss sums (a.ls), each also with the crop as
+// constants (k3_mid)
+static int launch_k3(const AsmPlan& p, const AsmArgs& a, const float2* U, void* out) {
+  const int Pw = p.g.Pw;
+  const bool loss = a.ls.stats != nullptr, mid = k3_mid(Pw, a);
+  PassKernel k = nullptr;
+  if (mid && Pw == Mx300::N) k = loss ? asm_rows_inv_loss_mid<Mx300::N> : asm_rows_inv_mid<Mx300::N>;
+  else if (mid && !loss) k = asm_rows_inv_mid<8192>;
+  else if (loss) on_rows(Pw, [&](auto N) { k = asm_rows_inv_loss<N()>; });
+  else on_rows(Pw, [&](auto N) { k = asm_rows_inv<N()>; });
+  KernelTimer kt("asm_rows_inv", p.s);
+  hipLaunchKernelGGL(k, dim3(a.nz * a.BC * a.Hout), dim3(rows_threads(Pw)), fft_lds_bytes_io(Pw), p.s, U, (float2*)out,
+                     p.pw, a);
+  THZ_LAUNCH_CHECK();
+  int e;
+  if (loss && (e = launch_loss_finish(a.ls, p.s))) return e;
+  kt.stop();
+  return THZ_OK;
+}
+
+// The z-x slice's column pass of the z-chunk, row R of the padded plane: T -> V (asm_cols' own task
+// split), or its Z-summing adjoint Gv -> U (one task per column).
+static int launch_cols_slice(const AsmPlan& p, AsmArgs& a, bool adjoint, const float2* src, float2* dst, int R) {
+  const AsmGeom& g = p.g;
+  const int th = threads_for(g.Ph);
+  const size_t lds = k2_lds_bytes(g.Ph);
+  void (*k)(const float2*, float2*, FftPlan, AsmArgs, int) = nullptr;
+  const bool served = on_pow2_only(g.Ph, [&](auto N) {
+    if (adjoint) k = asm_cols_slice_adj<N()>;
+    else k = asm_cols_slice<N()>;
+  });
+  if (!served) return fail(THZ_E_UNSUPPORTED, "z-x slice: no column pass for padded height %d", g.Ph);
+  a.zrec = !plane_recurrence_disabled();
+  KernelTimer kt(adjoint ? "asm_cols_slice_adj" : "asm_cols_slice", p.s);
+  const int ntask = adjoint ? g.ncols * g.BC : k2_tasks(g, &a, th, lds);
+  hipLaunchKernelGGL(k, dim3(ntask), dim3(th), lds, p.s, src, dst, p.ph, a, R);
+  THZ_LAUNCH_CHECK();
+  kt.stop();
+  return THZ_OK;
+}
+
+// the z-x slice's row pass: one row per (plane of the chunk, bc), V -> out
+static int launch_rows_slice(const AsmPlan& p, const AsmArgs& a, const float2* V, void* out) {
+  const int Pw = p.g.Pw;
+  PassKernel k = nullptr;
+  on_pow2(Pw, [&](auto N) { k = asm_rows_slice<N()>; });
+  KernelTimer kt("asm_rows_slice", p.s);
+  hipLaunchKernelGGL(k, dim3(a.nz * a.BC), dim3(threads_for(Pw)), fft_lds_bytes_io(Pw), p.s, V, (float2*)out, p.pw, a);
+  THZ_LAUNCH_CHECK();
+  kt.stop();
+  return THZ_OK;
+}
+
+// ---- the z-chunk loops -----------------------------------------------------------------------
+// The adjoint of a Z-plane forward (sum over planes): per z-chunk, K1 over the chunk's input
+// planes and the Z-summing K2; then K3 once on the summed plane.
+static int run_adjoint_sum(const AsmPlan& p, AsmArgs a, const void* in, void* out) {
+  float2 *T = (float2*)p.ws[0], *U = (float2*)p.ws[1];
+  int e;
+  a.zsum = 1;
+  a.tab_blocks = 0;  // K1 runs per chunk here: every chunk launches its tables itself
+  for (int z0 = 0; z0 < p.Z; z0 += p.g.zc) {
+    a.zoff = z0;
+    a.nz = std::min(p.g.zc, p.Z - z0);
+    a.zacc = z0 > 0;  // the chunks after the first add into U
+    if ((e = launch_k1(p, a, a.nz, in, T))) return e;
+    if ((e = launch_cols(p, a, a.sqt != nullptr, T, U))) return e;
+  }
+  a.zoff = 0;
+  a.nz = 1;
+  return launch_k3(p, a, U, out);
+}
+
+// K1 once, then (K2, K3) per z-chunk.  a.sqt is set where the column pass takes its tables from the
+// workspace (asm_forward_impl: the mixed-radix heights; the RSC pipeline brings a.tft instead).
+static int run_pipeline(const AsmPlan& p, const void* in, void* out) {
+  const AsmGeom& g = p.g;
+  float2 *T = (float2*)p.ws[0], *U = (float2*)p.ws[1];
+  AsmArgs a = p.a;
+  if (g.adj && p.Z > 1) return run_adjoint_sum(p, a, in, out);
+  int e;
+  const bool tables = a.sqt != nullptr;
+  // square 300-point grids (cfg4 / cfg5): the first z-chunk's column tables ride along with K1
+  // (tf_tables_body<PN> of K1's own size: Ph == Pw), one launch fewer per layer
+  a.tab_blocks = tables && g.Pw == g.Ph && g.Pw == Mx300::N ? g.C * g.ncols : 0;
+  a.zoff = 0;
+  a.nz = std::min(g.zc, p.Z);
+  if ((e = launch_k1(p, a, 1, in, T))) return e;
+  for (int z0 = 0; z0 < p.Z; z0 += g.zc) {
+    a.zoff = z0;
+    a.nz = std::min(g.zc, p.Z - z0);
+    if ((e = launch_cols(p, a, tables && !(z0 == 0 && a.tab_blocks), T, U))) return e;
+    if ((e = launch_k3(p, a, U, out))) return e;
+  }
+  return THZ_OK;
+}
 
 // K1 once, then (cols_slice, rows_slice) per z-chunk: row R of the padded plane
-static int run_slice(AsmArgs a, const AsmGeom& g, int Z, int R, const void* in, void* out, float2* T, float2* V,
-                     hipStream_t s, FftPlan pw, FftPlan ph) {
+static int run_slice(const AsmPlan& p, int R, const void* in, void* out) {
+  float2 *T = (float2*)p.ws[0], *V = (float2*)p.ws[1];
+  AsmArgs a = p.a;
   int e;
-  if ((e = ensure_lds_attr())) return e;
-  a.tab_blocks = 0;
+  const int zc = slice_zc(p.g);
   a.zoff = 0;
-  const int zc = slice_zc(g), th = threads_for(g.Ph);
-  a.nz = std::min(zc, Z);
-  {
-    KernelTimer kt("asm_rows_fwd", s);
-    THZ_ROWS_SWITCH(g.Pw, asm_rows_fwd, dim3(g.BC * g.Hin), fft_lds_bytes_io(g.Pw), s, (const float2*)in, T, pw, a);
-    THZ_LAUNCH_CHECK();
-    kt.stop();
-  }
-  const size_t lds2 = k2_lds_bytes(g.Ph);
-  a.zrec = !plane_recurrence_disabled();
-  for (int z0 = 0; z0 < Z; z0 += zc) {
+  a.nz = std::min(zc, p.Z);
+  if ((e = launch_k1(p, a, 1, in, T))) return e;
+  for (int z0 = 0; z0 < p.Z; z0 += zc) {
     a.zoff = z0;
-    a.nz = std::min(zc, Z - z0);
-    {
-      KernelTimer kt("asm_cols_slice", s);
-      const int ntask = k2_tasks(g, &a, th, lds2);  // asm_cols' own task split
-      THZ_POW2_ONLY_SWITCH(g.Ph, asm_cols_slice, dim3(ntask), dim3(th), lds2, s, (const float2*)T, V, ph, a, R);
-      THZ_LAUNCH_CHECK();
-      kt.stop();
-    }
-    {
-      KernelTimer kt("asm_rows_slice", s);
-      THZ_POW2_SWITCH(g.Pw, asm_rows_slice, dim3(a.nz * g.BC), dim3(threads_for(g.Pw)), fft_lds_bytes_io(g.Pw), s,
-                      (const float2*)V, (float2*)out, pw, a);
-      THZ_LAUNCH_CHECK();
-      kt.stop();
-    }
+    a.nz = std::min(zc, p.Z - z0);
+    if ((e = launch_cols_slice(p, a, false, T, V, R))) return e;
+    if ((e = launch_rows_slice(p, a, V, out))) return e;
   }
   return THZ_OK;
 }
 
-// the slice adjoint's workspace (g: the geometry of the adjoint descriptor, Hout x Wout the field):
-// the gradient spectrum U of one plane, in the layout asm_rows_inv reads, and Gv [Z][BC][ncb CB]
-static size_t slice_adj_u_bytes(const AsmGeom& g) {
-  return align256((size_t)g.BC * g.ncbu * CBU * u_rows(g.Hout) * sizeof(float2));
-}
-static size_t slice_adj_ws_bytes(const AsmGeom& g, int Z) {
-  return slice_adj_u_bytes(g) + align256((size_t)Z * g.BC * g.ncb * CB * sizeof(float2));
-}
-
-// row pass over the Z BC cotangent rows, the Z-summing column pass, asm_rows_inv once
-static int run_slice_adjoint(AsmArgs a, const AsmGeom& g, int Z, int R, const void* gout, void* gin, float2* U,
-                             float2* Gv, hipStream_t s, FftPlan pw, FftPlan ph) {
+// row pass over the Z BC cotangent rows, the Z-summing column pass, K3 once: no loop, the column
+// pass segments the planes itself
+static int run_slice_adjoint(const AsmPlan& p, int R, const void* gout, void* gin) {
+  float2 *U = (float2*)p.ws[0], *Gv = (float2*)p.ws[1];
+  AsmArgs a = p.a;
   int e;
-  if ((e = ensure_lds_attr())) return e;
-  a.tab_blocks = 0;
   a.zoff = 0;
-  a.nz = Z;
-  {
-    // each cotangent row is a one-row plane: Gv[z][bc] is T of plane z BC + bc with Hin = 1
-    KernelTimer kt("asm_rows_fwd", s);
-    AsmArgs a1 = a;
-    a1.Hin = 1;
-    a1.in_r0 = 0;
-    THZ_ROWS_SWITCH(g.Pw, asm_rows_fwd, dim3(Z * g.BC), fft_lds_bytes_io(g.Pw), s, (const float2*)gout, Gv, pw, a1);
-    THZ_LAUNCH_CHECK();
-    kt.stop();
-  }
-  {
-    KernelTimer kt("asm_cols_slice_adj", s);
-    const size_t lds2 = k2_lds_bytes(g.Ph);
-    a.zrec = !plane_recurrence_disabled();
-    THZ_POW2_ONLY_SWITCH(g.Ph, asm_cols_slice_adj, dim3(g.ncols * g.BC), dim3(threads_for(g.Ph)), lds2, s,
-                         (const float2*)Gv, U, ph, a, R);
-    THZ_LAUNCH_CHECK();
-    kt.stop();
-  }
+  a.nz = p.Z;
+  // each cotangent row is a one-row plane: Gv[z][bc] is T of plane z BC + bc with Hin = 1
+  AsmArgs a1 = a;
+  a1.Hin = 1;
+  a1.in_r0 = 0;
+  if ((e = launch_k1(p, a1, p.Z, gout, Gv))) return e;
+  if ((e = launch_cols_slice(p, a, true, Gv, U, R))) return e;
   a.nz = 1;
-  {
-    KernelTimer kt("asm_rows_inv", s);
-    THZ_ROWS_SWITCH(g.Pw, asm_rows_inv, dim3(g.BC * g.Hout), fft_lds_bytes_io(g.Pw), s, (const float2*)U, (float2*)gin,
-                    pw, a);
-    THZ_LAUNCH_CHECK();
-    kt.stop();
-  }
-  return THZ_OK;
+  return launch_k3(p, a, U, gin);
 }
 
 // what thz_asm_slice_* accept, checked on the host before any device call
-static int validate_slice(const thz_asm_desc* d, bool adjoint = false) {
+static int validate_slice(const thz_asm_desc* d, bool adjoint) {
   int e = validate(d);
   if (e) return e;
   if (adjoint && d->adjoint != 1) return fail(THZ_E_ARG, "the z-x slice adjoint takes adjoint == 1");
@@ -2096,69 +2095,76 @@ static int validate_slice(const thz_asm_desc* d, bool adjoint = false) {
                                    "(slice thz_asm_forward's planes instead)", Ph);
   return THZ_OK;
 }
+static int validate_pipe(const thz_asm_desc* d, Pipe pipe) {
+  return pipe == Pipe::Planes ? validate(d) : validate_slice(d, pipe == Pipe::SliceAdjoint);
+}
+
+// The prelude of every entry that launches: the descriptor's validation, the geometry, the slices'
+// row (of the forward's output grid), the data pointers (data_ok), the workspace against the
+// pipeline's layout, the device plans and the argument block -- all host checks before any device call.
+static int asm_plan(const thz_asm_desc* d, Pipe pipe, int row, bool data_ok, void* workspace, size_t bytes,
+                    thz_stream_t stream, AsmPlan* p) {
+  int e = validate_pipe(d, pipe);
+  if (e) return e;
+  AsmGeom& g = p->g;
+  geometry(d, &g);
+  if (pipe != Pipe::Planes) {
+    // adjoint descriptor: Hin x Win is the forward's output grid, Hout x Wout the field
+    const int rows = pipe == Pipe::Slice ? g.Hout : g.Hin;
+    if (row < 0 || row >= rows)
+      return fail(THZ_E_ARG, "z-x slice%s: row %d outside [0, %d)", pipe == Pipe::Slice ? "" : " adjoint", row, rows);
+  }
+  if (!data_ok) return fail(THZ_E_ARG, "null data pointer");
+  const WsLayout lay = ws_layout(pipe, g, d->Z);
+  if ((e = check_workspace(workspace, bytes, lay.total()))) return e;
+  if ((e = device_plans(g, &p->pw, &p->ph))) return e;
+  char* w = (char*)workspace;
+  for (int i = 0; i < 3; ++i) {
+    p->ws[i] = lay.part[i] ? w : nullptr;
+    w += lay.part[i];
+  }
+  p->a = asm_args_base(d, g);
+  p->s = (hipStream_t)stream;
+  p->Z = d->Z;
+  return THZ_OK;
+}
+
+static int asm_workspace_size(const thz_asm_desc* d, Pipe pipe, size_t* bytes) {
+  int e = validate_pipe(d, pipe);
+  if (e) return e;
+  if (!bytes) return fail(THZ_E_ARG, "null bytes");
+  AsmGeom g;
+  geometry(d, &g);
+  *bytes = ws_layout(pipe, g, d->Z).total();
+  return THZ_OK;
+}
 
 }  // namespace thz
 
 using namespace thz;
 
 extern "C" int thz_asm_slice_workspace_size(const thz_asm_desc* d, size_t* bytes) {
-  int e = validate_slice(d);
-  if (e) return e;
-  if (!bytes) return fail(THZ_E_ARG, "null bytes");
-  AsmGeom g;
-  geometry(d, &g);
-  *bytes = slice_ws_bytes(g);
-  return THZ_OK;
+  return asm_workspace_size(d, Pipe::Slice, bytes);
 }
 
 extern "C" int thz_asm_slice_forward(const thz_asm_desc* d, int row, const void* in, void* out, void* workspace,
                                      size_t workspace_bytes, thz_stream_t stream) {
-  int e = validate_slice(d);
+  AsmPlan p;
+  int e = asm_plan(d, Pipe::Slice, row, in && out, workspace, workspace_bytes, stream, &p);
   if (e) return e;
-  AsmGeom g;
-  geometry(d, &g);
-  if (row < 0 || row >= g.Hout) return fail(THZ_E_ARG, "z-x slice: row %d outside [0, %d)", row, g.Hout);
-  if (!in || !out) return fail(THZ_E_ARG, "null data pointer");
-  const size_t need = slice_ws_bytes(g);
-  if (!workspace || workspace_bytes < need)
-    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
-  FftPlan pw, ph;
-  if ((e = get_plan(g.Pw, &pw))) return e;
-  if ((e = get_plan(g.Ph, &ph))) return e;
-  const AsmArgs a = asm_args_base(d, g);
-  float2* T = (float2*)workspace;
-  float2* V = (float2*)((char*)workspace + t_bytes(g));
-  return run_slice(a, g, d->Z, row + a.out_r0, in, out, T, V, (hipStream_t)stream, pw, ph);
+  return run_slice(p, row + p.a.out_r0, in, out);
 }
 
 extern "C" int thz_asm_slice_adjoint_workspace_size(const thz_asm_desc* d, size_t* bytes) {
-  int e = validate_slice(d, true);
-  if (e) return e;
-  if (!bytes) return fail(THZ_E_ARG, "null bytes");
-  AsmGeom g;
-  geometry(d, &g);
-  *bytes = slice_adj_ws_bytes(g, d->Z);
-  return THZ_OK;
+  return asm_workspace_size(d, Pipe::SliceAdjoint, bytes);
 }
 
 extern "C" int thz_asm_slice_adjoint(const thz_asm_desc* d, int row, const void* grad_out, void* grad_in,
                                      void* workspace, size_t workspace_bytes, thz_stream_t stream) {
-  int e = validate_slice(d, true);
+  AsmPlan p;
+  int e = asm_plan(d, Pipe::SliceAdjoint, row, grad_out && grad_in, workspace, workspace_bytes, stream, &p);
   if (e) return e;
-  AsmGeom g;
-  geometry(d, &g);  // adjoint: Hin x Win the forward's output grid, Hout x Wout the field
-  if (row < 0 || row >= g.Hin) return fail(THZ_E_ARG, "z-x slice adjoint: row %d outside [0, %d)", row, g.Hin);
-  if (!grad_out || !grad_in) return fail(THZ_E_ARG, "null data pointer");
-  const size_t need = slice_adj_ws_bytes(g, d->Z);
-  if (!workspace || workspace_bytes < need)
-    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
-  FftPlan pw, ph;
-  if ((e = get_plan(g.Pw, &pw))) return e;
-  if ((e = get_plan(g.Ph, &ph))) return e;
-  const AsmArgs a = asm_args_base(d, g);
-  float2* U = (float2*)workspace;
-  float2* Gv = (float2*)((char*)workspace + slice_adj_u_bytes(g));
-  return run_slice_adjoint(a, g, d->Z, row + a.in_r0, grad_out, grad_in, U, Gv, (hipStream_t)stream, pw, ph);
+  return run_slice_adjoint(p, row + p.a.in_r0, grad_out, grad_in);
 }
 
 extern "C" int thz_asm_band(const thz_asm_desc* d, int* ncols, int* z_chunk) {
@@ -2172,38 +2178,58 @@ extern "C" int thz_asm_band(const thz_asm_desc* d, int* ncols, int* z_chunk) {
 }
 
 extern "C" int thz_asm_workspace_size(const thz_asm_desc* d, size_t* bytes) {
-  int e = validate(d);
-  if (e) return e;
-  if (!bytes) return fail(THZ_E_ARG, "null bytes");
-  AsmGeom g;
-  geometry(d, &g);
-  *bytes = ws_bytes(g);
-  return THZ_OK;
+  return asm_workspace_size(d, Pipe::Planes, bytes);
 }
 
 namespace thz {
-static int asm_forward_impl(const thz_asm_desc* d, const thz_doe_desc* m, const float* mh, const float* mu,
-                            float* mhfull, const void* in, void* out, void* workspace, size_t workspace_bytes,
-                            thz_stream_t stream, const LossSink* ls = nullptr, const thz_loss_desc* lg = nullptr,
-                            const float2* lg_field = nullptr, const float* lg_target = nullptr,
-                            const float* lg_stats = nullptr, const float* lg_gloss = nullptr) {
-  int e = validate(d);
-  if (e) return e;
-  if ((!in && !lg_field) || !out) return fail(THZ_E_ARG, "null data pointer");
-  AsmGeom g;
-  geometry(d, &g);
-  const size_t need = ws_bytes(g);
-  if (!workspace || workspace_bytes < need)
-    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
-  FftPlan pw, ph;
-  if ((e = get_plan(g.Pw, &pw))) return e;
-  if ((e = get_plan(g.Ph, &ph))) return e;
+// The optional parts of a planes pipeline; an empty one is thz_asm_forward.
+struct AsmFused {
+  // DOE modulation in K1's loader (desc null: none)
+  struct {
+    const thz_doe_desc* desc;
+    const float *height, *noise;
+    float* height_full;
+  } mod{};
+  const LossSink* loss = nullptr;  // the loss sums in K3's storer
+  // the adjoint starts from the loss gradient at the stored forward output `field` (null: none)
+  struct {
+    const thz_loss_desc* desc;
+    const float2* field;
+    const float *target, *stats, *gloss;
+  } grad{};
+};
 
-  AsmArgs a = asm_args_base(d, g);
-  if (m) {
-    a.mod_h = mh;
-    a.mod_u = mu;
-    a.mod_hfull = mhfull;
+// the field a fused DOE modulates is the ASM input
+static int check_doe_desc(const thz_asm_desc* d, const thz_doe_desc* m) {
+  if (m->B != d->B || m->C != d->C || m->H != d->H || m->W != d->W)
+    return fail(THZ_E_ARG, "DOE field %dx%dx%dx%d does not match the ASM input %dx%dx%dx%d", m->B, m->C, m->H, m->W,
+                d->B, d->C, d->H, d->W);
+  if (m->hs < 1 || m->ws < 1) return fail(THZ_E_ARG, "bad height-map size %dx%d", m->hs, m->ws);
+  return THZ_OK;
+}
+
+// the field of a fused loss is the ASM output (Z B plane-major items), and the target broadcasts over it
+static int check_loss_desc(const thz_asm_desc* d, const thz_loss_desc* l) {
+  const int Ho = d->unpad ? d->H : d->H + 2 * d->pad_h, Wo = d->unpad ? d->W : d->W + 2 * d->pad_w;
+  if (l->B != d->Z * d->B || l->C != d->C || l->H != Ho || l->W != Wo)
+    return fail(THZ_E_ARG, "loss field %dx%dx%dx%d does not match the ASM output %dx%dx%dx%d", l->B, l->C, l->H, l->W,
+                d->B, d->C, Ho, Wo);
+  if (!(l->tB == 1 || l->tB == l->B) || !(l->tC == 1 || l->tC == l->C))
+    return fail(THZ_E_ARG, "target %dx%d does not broadcast over %dx%d", l->tB, l->tC, l->B, l->C);
+  return THZ_OK;
+}
+
+static int asm_forward_impl(const thz_asm_desc* d, const void* in, void* out, void* workspace, size_t workspace_bytes,
+                            thz_stream_t stream, const AsmFused& f) {
+  AsmPlan p;
+  int e = asm_plan(d, Pipe::Planes, 0, (in || f.grad.field) && out, workspace, workspace_bytes, stream, &p);
+  if (e) return e;
+  const AsmGeom& g = p.g;
+  AsmArgs& a = p.a;
+  if (const thz_doe_desc* m = f.mod.desc) {
+    a.mod_h = f.mod.height;
+    a.mod_u = f.mod.noise;
+    a.mod_hfull = f.mod.height_full;
     a.mod_hs = m->hs;
     a.mod_ws = m->ws;
     a.mod_tol = m->tolerance;
@@ -2223,34 +2249,35 @@ static int asm_forward_impl(const thz_asm_desc* d, const thz_doe_desc* m, const 
     a.ap_side = d->adjoint ? 2 : 1;
     // carried by the 300-point row passes only (the K3 storer forward, the K1 loader adjoint:
     // asm_rows_inv<300> / asm_rows_fwd<300>)
-    if (mx_kind(g.Pw) != Mx300::N)
+    if (g.Pw != Mx300::N)
       return fail(THZ_E_UNSUPPORTED, "window mask: only the 300-point row passes fold the aperture; "
                                      "apply it separately");
     if (d->adjoint && d->Z > 1)
       return fail(THZ_E_UNSUPPORTED, "window mask: one z-plane per adjoint call");
   }
-  if (ls) a.ls = *ls;
-  if (lg_field) {  // the adjoint pipeline starts from the loss gradient
-    a.lg_field = lg_field;
-    a.lg_gloss = lg_gloss;
-    a.lg_target = lg_target;
-    a.lg_stats = lg_stats;
+  if (f.loss) a.ls = *f.loss;
+  if (f.grad.field) {  // the adjoint pipeline starts from the loss gradient
+    const thz_loss_desc* lg = f.grad.desc;
+    a.lg_field = f.grad.field;
+    a.lg_gloss = f.grad.gloss;
+    a.lg_target = f.grad.target;
+    a.lg_stats = f.grad.stats;
     a.lg_tB = lg->tB;
     a.lg_tC = lg->tC;
     // the loss of a Z-plane pipeline is the sum of the planes' means (thz_asm_forward_loss)
     a.lg_two_inv_n = (float)(2.0 * d->Z / ((double)lg->B * lg->C * lg->H * lg->W));
   }
-
-  float2* T = (float2*)workspace;
-  float2* U = (float2*)((char*)workspace + t_bytes(g));
-  char* tabs = (char*)workspace + ws_bytes(g) - tab_bytes(g);
-  return run_pipeline(a, g, d->Z, in, out, T, U, (hipStream_t)stream, pw, ph, tab_bytes(g) ? tabs : nullptr);
+  if (p.ws[2]) {  // the mixed-radix heights: the column pass's tables (tab_bytes: sqt, then mzt)
+    a.sqt = (float*)p.ws[2];
+    a.mzt = (int*)(p.ws[2] + tab_sq_bytes(g));
+  }
+  return run_pipeline(p, in, out);
 }
 }  // namespace thz
 
 extern "C" int thz_asm_forward(const thz_asm_desc* d, const void* in, void* out, void* workspace,
                                size_t workspace_bytes, thz_stream_t stream) {
-  return asm_forward_impl(d, nullptr, nullptr, nullptr, nullptr, in, out, workspace, workspace_bytes, stream);
+  return asm_forward_impl(d, in, out, workspace, workspace_bytes, stream, AsmFused{});
 }
 
 namespace thz {
@@ -2275,15 +2302,8 @@ extern "C" int thz_asm_transfer_function(const thz_asm_desc* d, void* out, thz_s
   if (!d->z) return fail(THZ_E_ARG, "the transfer-function table takes a host z");
   AsmGeom g;
   geometry(d, &g);
-  AsmArgs a{};
-  a.C = d->C;
-  a.Ph = g.Ph;
-  a.Pw = g.Pw;
-  a.bl = d->bandlimit;
-  a.dx = d->dx;
-  a.dy = d->dy;
-  for (int c = 0; c < d->C; ++c) a.lam[c] = d->wavelengths[c];
-  a.zv[0] = d->z[0];
+  AsmArgs a = asm_args_base(d, g);
+  a.adjoint = 0;  // the table is H itself whatever the descriptor's direction
   hipStream_t s = (hipStream_t)stream;
   KernelTimer kt("asm_tf_export", s);
   hipLaunchKernelGGL(asm_tf_export, dim3((g.Pw + 255) / 256, g.Ph, d->C), dim3(256), 0, s, (float2*)out, a);
@@ -2297,11 +2317,11 @@ extern "C" int thz_asm_forward_modulated(const thz_asm_desc* d, const thz_doe_de
                                          void* workspace, size_t workspace_bytes, thz_stream_t stream) {
   if (!d || !m || !height) return fail(THZ_E_ARG, "null descriptor / height");
   if (d->adjoint) return fail(THZ_E_ARG, "the fused DOE modulation is forward only");
-  if (m->B != d->B || m->C != d->C || m->H != d->H || m->W != d->W)
-    return fail(THZ_E_ARG, "DOE field %dx%dx%dx%d does not match the ASM input %dx%dx%dx%d", m->B, m->C, m->H, m->W,
-                d->B, d->C, d->H, d->W);
-  if (m->hs < 1 || m->ws < 1) return fail(THZ_E_ARG, "bad height-map size %dx%d", m->hs, m->ws);
-  return asm_forward_impl(d, m, height, noise, height_full, field, out, workspace, workspace_bytes, stream);
+  int e = check_doe_desc(d, m);
+  if (e) return e;
+  AsmFused f;
+  f.mod = {m, height, noise, height_full};
+  return asm_forward_impl(d, field, out, workspace, workspace_bytes, stream, f);
 }
 
 extern "C" int thz_asm_adjoint_loss(const thz_asm_desc* d, const thz_loss_desc* l, const void* field,
@@ -2313,14 +2333,10 @@ extern "C" int thz_asm_adjoint_loss(const thz_asm_desc* d, const thz_loss_desc* 
   if (!l || !field || !target || !stats || !grad_loss || !grad_in)
     return fail(THZ_E_ARG, "null loss descriptor / field / target / stats / grad_loss / grad_in");
   if (!d->adjoint) return fail(THZ_E_ARG, "the fused loss adjoint takes adjoint == 1");
-  const int Ho = d->unpad ? d->H : d->H + 2 * d->pad_h, Wo = d->unpad ? d->W : d->W + 2 * d->pad_w;
-  if (l->B != d->Z * d->B || l->C != d->C || l->H != Ho || l->W != Wo)
-    return fail(THZ_E_ARG, "loss field %dx%dx%dx%d does not match the ASM output %dx%dx%dx%d", l->B, l->C, l->H, l->W,
-                d->B, d->C, Ho, Wo);
-  if (!(l->tB == 1 || l->tB == l->B) || !(l->tC == 1 || l->tC == l->C))
-    return fail(THZ_E_ARG, "target %dx%d does not broadcast over %dx%d", l->tB, l->tC, l->B, l->C);
-  return asm_forward_impl(d, nullptr, nullptr, nullptr, nullptr, grad_out, grad_in, workspace, workspace_bytes, stream,
-                          nullptr, l, (const float2*)field, target, stats, grad_loss);
+  if ((e = check_loss_desc(d, l))) return e;
+  AsmFused f;
+  f.grad = {l, (const float2*)field, target, stats, grad_loss};
+  return asm_forward_impl(d, grad_out, grad_in, workspace, workspace_bytes, stream, f);
 }
 
 extern "C" int thz_asm_forward_loss(const thz_asm_desc* d, const thz_doe_desc* m, const void* field,
@@ -2331,22 +2347,16 @@ extern "C" int thz_asm_forward_loss(const thz_asm_desc* d, const thz_doe_desc* m
   if (e) return e;
   if (!l || !target || !loss || !stats) return fail(THZ_E_ARG, "null loss descriptor / target / loss / stats");
   if (d->adjoint) return fail(THZ_E_ARG, "the fused loss is forward only (thz_asm_adjoint_loss)");
-  const int Ho = d->unpad ? d->H : d->H + 2 * d->pad_h, Wo = d->unpad ? d->W : d->W + 2 * d->pad_w;
-  if (l->B != d->Z * d->B || l->C != d->C || l->H != Ho || l->W != Wo)
-    return fail(THZ_E_ARG, "loss field %dx%dx%dx%d does not match the ASM output %dx%dx%dx%d", l->B, l->C, l->H, l->W,
-                d->B, d->C, Ho, Wo);
-  if (!(l->tB == 1 || l->tB == l->B) || !(l->tC == 1 || l->tC == l->C))
-    return fail(THZ_E_ARG, "target %dx%d does not broadcast over %dx%d", l->tB, l->tC, l->B, l->C);
+  if ((e = check_loss_desc(d, l))) return e;
+  AsmFused f;
   if (m) {
     if (!height) return fail(THZ_E_ARG, "null height map");
-    if (m->B != d->B || m->C != d->C || m->H != d->H || m->W != d->W)
-      return fail(THZ_E_ARG, "DOE field %dx%dx%dx%d does not match the ASM input %dx%dx%dx%d", m->B, m->C, m->H,
-                  m->W, d->B, d->C, d->H, d->W);
-    if (m->hs < 1 || m->ws < 1) return fail(THZ_E_ARG, "bad height-map size %dx%d", m->hs, m->ws);
+    if ((e = check_doe_desc(d, m))) return e;
+    f.mod = {m, height, noise, height_full};
   }
   const LossSink ls = loss_sink(l, target, loss, stats, l->C * l->H, d->Z);
-  return asm_forward_impl(d, m, m ? height : nullptr, m ? noise : nullptr, m ? height_full : nullptr, field, out,
-                          workspace, workspace_bytes, stream, &ls);
+  f.loss = &ls;
+  return asm_forward_impl(d, field, out, workspace, workspace_bytes, stream, f);
 }
 
 namespace thz {
@@ -2357,8 +2367,10 @@ int fft_rows_strided(const void* in, void* out, int rows, int n, size_t stride, 
   int e = get_plan(n, &p);
   if (e) return e;
   if ((e = ensure_lds_attr())) return e;
-  THZ_POW2_SWITCH(n, fft_rows_kernel, dim3(rows), dim3(threads_for(n)), fft_lds_bytes_io(n), s, (const float2*)in,
-                  (float2*)out, p, inverse, stride);
+  on_pow2(n, [&](auto N) {
+    hipLaunchKernelGGL(fft_rows_kernel<N()>, dim3(rows), dim3(threads_for(n)), fft_lds_bytes_io(n), s,
+                       (const float2*)in, (float2*)out, p, inverse, stride);
+  });
   THZ_LAUNCH_CHECK();
   return THZ_OK;
 }
@@ -2376,7 +2388,8 @@ namespace thz {
 struct RscPlan {
   AsmGeom g;
   RscKArgs k;
-  size_t tk, kf, t, u;  // byte sizes
+  size_t tk, kf, t, u;  // byte sizes: the kernel's row pass | its spectrum (a.tft) | T | U
+  size_t total() const { return tk + kf + t + u; }
 };
 
 static int rsc_plan(const thz_rsc_desc* d, RscPlan* p) {
@@ -2412,8 +2425,8 @@ static int rsc_plan(const thz_rsc_desc* d, RscPlan* p) {
   for (int c = 0; c < d->C; ++c) k.lam[c] = d->wavelengths[c];
   p->tk = align256((size_t)d->C * k.ncbK * CB * g.Ph * sizeof(float2));
   p->kf = align256((size_t)d->C * g.Pw * g.Ph * sizeof(float2));
-  p->t = align256((size_t)g.BC * g.ncb * CB * g.Hin * sizeof(float2));
-  p->u = align256((size_t)g.BC * g.ncbu * CBU * u_rows(g.Hout) * sizeof(float2));
+  p->t = t_bytes(g);
+  p->u = u_bytes(g, 1);
   return THZ_OK;
 }
 
@@ -2424,7 +2437,7 @@ extern "C" int thz_rsc_workspace_size(const thz_rsc_desc* d, size_t* bytes) {
   int e = rsc_plan(d, &p);
   if (e) return e;
   if (!bytes) return fail(THZ_E_ARG, "null bytes");
-  *bytes = p.tk + p.kf + p.t + p.u;
+  *bytes = p.total();
   return THZ_OK;
 }
 
@@ -2434,55 +2447,47 @@ extern "C" int thz_rsc_forward(const thz_rsc_desc* d, const void* in, void* out,
   int e = rsc_plan(d, &p);
   if (e) return e;
   if (!in || !out) return fail(THZ_E_ARG, "null data pointer");
-  if (!workspace || workspace_bytes < p.tk + p.kf + p.t + p.u)
-    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, p.tk + p.kf + p.t + p.u);
-  if ((e = ensure_lds_attr())) return e;
-  const AsmGeom& g = p.g;
-  FftPlan pw, ph;
-  if ((e = get_plan(g.Pw, &pw))) return e;
-  if ((e = get_plan(g.Ph, &ph))) return e;
-  hipStream_t s = (hipStream_t)stream;
+  if ((e = check_workspace(workspace, workspace_bytes, p.total()))) return e;
+  AsmPlan ap;
+  ap.g = p.g;
+  const AsmGeom& g = ap.g;
+  if ((e = device_plans(g, &ap.pw, &ap.ph))) return e;
+  hipStream_t s = ap.s = (hipStream_t)stream;
   char* w = (char*)workspace;
   float2* TK = (float2*)w;
   float2* KF = (float2*)(w + p.tk);
-  float2* T = (float2*)(w + p.tk + p.kf);
-  float2* U = (float2*)(w + p.tk + p.kf + p.t);
+  ap.ws[0] = w + p.tk + p.kf;         // T
+  ap.ws[1] = w + p.tk + p.kf + p.t;   // U
+  ap.ws[2] = nullptr;                 // no column tables: the transfer function is KF
+  ap.Z = 1;
   {
     KernelTimer kt("rsc_kernel_fft", s);
-    THZ_POW2_SWITCH(g.Pw, rsc_k_rows, dim3(d->C * g.Ph), dim3(threads_for(g.Pw)), fft_lds_bytes_io(g.Pw), s, TK, pw,
-                    p.k);
+    on_pow2(g.Pw, [&](auto N) {
+      hipLaunchKernelGGL(rsc_k_rows<N()>, dim3(d->C * g.Ph), dim3(threads_for(g.Pw)), fft_lds_bytes_io(g.Pw), s, TK,
+                         ap.pw, p.k);
+    });
     THZ_LAUNCH_CHECK();
-    THZ_POW2_SWITCH(g.Ph, rsc_k_cols, dim3(d->C * g.Pw), dim3(threads_for(g.Ph)), fft_lds_bytes_io(g.Ph), s,
-                    (const float2*)TK, KF, ph, p.k);
+    on_pow2(g.Ph, [&](auto N) {
+      hipLaunchKernelGGL(rsc_k_cols<N()>, dim3(d->C * g.Pw), dim3(threads_for(g.Ph)), fft_lds_bytes_io(g.Ph), s,
+                         (const float2*)TK, KF, ap.ph, p.k);
+    });
     THZ_LAUNCH_CHECK();
     kt.stop();
   }
-  AsmArgs a{};
-  a.BC = g.BC;
-  a.C = d->C;
-  a.Ph = g.Ph;
-  a.Pw = g.Pw;
-  if (!d->adjoint) {
-    a.in_r0 = 0; a.in_c0 = 0; a.Hin = d->H; a.Win = d->W;         // U[..., :H, :W] = field (:198-200)
-    a.out_r0 = d->H; a.out_c0 = d->W; a.Hout = g.Hout; a.Wout = g.Wout;
+  // the shared base, then what the convolution changes: its windows in the doubled plane, no band
+  // limit, the quadrature weight in the scale, the kernel's spectrum as the transfer function, Ez
+  AsmArgs& a = ap.a = args_base(g, THZ_BANDLIMIT_NONE, d->dx, d->dy, d->wavelengths);
+  if (!d->adjoint) {  // U[..., :H, :W] = field (:198-200), read back from [H:, W:]
+    a.out_r0 = d->H; a.out_c0 = d->W;
   } else {  // adjoint: gradient placed at [H:, W:], result read back from [:H, :W]
-    a.in_r0 = d->H; a.in_c0 = d->W; a.Hin = g.Hin; a.Win = g.Win;
-    a.out_r0 = 0; a.out_c0 = 0; a.Hout = g.Hout; a.Wout = g.Wout;
+    a.in_r0 = d->H; a.in_c0 = d->W;
     a.adjoint = 1;
   }
-  a.ncols = g.ncols;
-  a.ncb = g.ncb;
-  a.ncbu = g.ncbu;
-  a.J = g.J;
-  a.bl = THZ_BANDLIMIT_NONE;
-  a.dx = d->dx;
-  a.dy = d->dy;
   a.scale = (float)((double)d->dx * (double)d->dy / ((double)g.Ph * (double)g.Pw));
   a.tft = KF;
   a.vec = d->vectorial;
   a.zr = d->z;
-  a.lam[0] = d->wavelengths[0];
-  for (int c = 0; c < d->C; ++c) a.lam[c] = d->wavelengths[c];
   a.zv[0] = d->z;
-  return run_pipeline(a, g, 1, in, out, T, U, s, pw, ph);
+  return run_pipeline(ap, in, out);
 }
+

@@ -43,6 +43,25 @@ def _stream_handle():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _launch(size_fn, run_fn, d, device, *args):
+    """One call of a workspace-taking entry point on ``device``'s current stream:
+    run_fn(&d, *args, workspace, bytes, stream) with the workspace size_fn(&d) asks for.  Tensors
+    among ``args`` pass as their data pointers, None as NULL, anything else (a row, a byref'd
+    descriptor) as it is."""
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(size_fn(ctypes.byref(d), ctypes.byref(nbytes)))
+    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=device)
+    args = [ctypes.c_void_p(a.data_ptr()) if torch.is_tensor(a) else a for a in args]
+    with torch.cuda.device(device):
+        _lib.check(run_fn(ctypes.byref(d), *args, ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
+                          _stream_handle()))
+
+
+def _bandlimit(b):
+    """thz_asm_desc.bandlimit: the code itself, or the code of a name (_lib.BANDLIMIT)."""
+    return b if isinstance(b, int) else _lib.BANDLIMIT[b]
+
+
 def asm_padding(H, W, padding_scale, do_padding=True):
     """pad = floor(s N / 2), P = N + 2 pad (Props/ASM_Prop.py:119-136)."""
     if not do_padding:
@@ -100,28 +119,26 @@ def asm_apply(data, wavelengths, spacing, zs, pad_h, pad_w, unpad, bandlimit, ad
         raise TypeError(f"ASM kernels compute in complex64 or complex128; got {data.dtype}")
     L = _lib.lib()
     data = data.contiguous()
+    (B, C, H, W), out_shape = _asm_shapes(data, zs, pad_h, pad_w, unpad, adjoint)
+    d = _asm_desc(B, C, H, W, pad_h, pad_w, unpad, bandlimit, wavelengths, spacing, zs, adjoint, z_chunk, mask, z_dev)
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.complex64, device=data.device)
+    _launch(L.thz_asm_workspace_size, L.thz_asm_forward, d, data.device, data, out)
+    return out
+
+
+def _asm_shapes(data, zs, pad_h, pad_w, unpad, adjoint):
+    """(field shape (B, C, H, W), output shape) of an ASM launch on ``data``: the field itself
+    forward, the [Z,B,C,Ho,Wo] cotangent of its planes in the adjoint."""
     if adjoint:
         Z, B, C, Ho, Wo = data.shape
         if Z != len(zs):
             raise ValueError(f"adjoint: {Z} gradient planes for {len(zs)} z values")
-        H = Ho - (0 if unpad else 2 * pad_h)
-        W = Wo - (0 if unpad else 2 * pad_w)
-        out_shape = (B, C, H, W)
-    else:
-        B, C, H, W = data.shape
-        Ho, Wo = (H, W) if unpad else (H + 2 * pad_h, W + 2 * pad_w)
-        out_shape = (len(zs), B, C, Ho, Wo)
-    d = _asm_desc(B, C, H, W, pad_h, pad_w, unpad, bandlimit, wavelengths, spacing, zs, adjoint, z_chunk, mask, z_dev)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.thz_asm_workspace_size(ctypes.byref(d), ctypes.byref(nbytes)))
-    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=data.device)
-    if out is None:
-        out = torch.empty(out_shape, dtype=torch.complex64, device=data.device)
-    with torch.cuda.device(data.device):
-        _lib.check(L.thz_asm_forward(ctypes.byref(d), ctypes.c_void_p(data.data_ptr()),
-                                     ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                     ctypes.c_size_t(ws.numel()), _stream_handle()))
-    return out
+        field = (B, C, Ho - (0 if unpad else 2 * pad_h), Wo - (0 if unpad else 2 * pad_w))
+        return field, field
+    B, C, H, W = data.shape
+    Ho, Wo = (H, W) if unpad else (H + 2 * pad_h, W + 2 * pad_w)
+    return (B, C, H, W), (len(zs), B, C, Ho, Wo)
 
 
 ASM_SLICE_HEIGHTS = (1024, 2048, 4096, 8192, 16384)  # padded heights thz_asm_slice_forward serves
@@ -146,17 +163,11 @@ def asm_slice_apply(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, ba
     B, C, H, W = data.shape
     Wo = W if unpad else W + 2 * pad_w
     d = _asm_desc(B, C, H, W, pad_h, pad_w, unpad, bandlimit, wavelengths, spacing, zs, False)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.thz_asm_slice_workspace_size(ctypes.byref(d), ctypes.byref(nbytes)))
-    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=data.device)
     if out is None:
         out = torch.empty((len(zs), B, C, Wo), dtype=torch.complex64, device=data.device)
     elif tuple(out.shape) != (len(zs), B, C, Wo) or out.dtype != torch.complex64 or not out.is_contiguous():
         raise ValueError(f"ASM slice: out must be a contiguous complex64 {(len(zs), B, C, Wo)} tensor")
-    with torch.cuda.device(data.device):
-        _lib.check(L.thz_asm_slice_forward(ctypes.byref(d), int(row), ctypes.c_void_p(data.data_ptr()),
-                                           ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                           ctypes.c_size_t(ws.numel()), _stream_handle()))
+    _launch(L.thz_asm_slice_workspace_size, L.thz_asm_slice_forward, d, data.device, int(row), data, out)
     return out
 
 
@@ -176,14 +187,8 @@ def asm_slice_adjoint(g, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, ban
         raise ValueError(f"ASM slice adjoint: {Z} gradient rows for {len(zs)} z values")
     H, W = int(height), Wo - (0 if unpad else 2 * pad_w)
     d = _asm_desc(B, C, H, W, pad_h, pad_w, unpad, bandlimit, wavelengths, spacing, zs, True)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.thz_asm_slice_adjoint_workspace_size(ctypes.byref(d), ctypes.byref(nbytes)))
-    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=g.device)
     gin = torch.empty((B, C, H, W), dtype=torch.complex64, device=g.device)
-    with torch.cuda.device(g.device):
-        _lib.check(L.thz_asm_slice_adjoint(ctypes.byref(d), int(row), ctypes.c_void_p(g.data_ptr()),
-                                           ctypes.c_void_p(gin.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                           ctypes.c_size_t(ws.numel()), _stream_handle()))
+    _launch(L.thz_asm_slice_adjoint_workspace_size, L.thz_asm_slice_adjoint, d, g.device, int(row), g, gin)
     return gin
 
 
@@ -207,7 +212,7 @@ def asm_propagate_zx(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad=Tr
     """Differentiable z-x slice on the slice kernels, forward and backward: [B,C,H,W] complex64 ->
     [Z,B,C,Wo], output row ``row`` of every plane of ``zs`` (any length: chunks of THZ_MAX_Z planes).
     The padded height must be one the slice kernels serve (asm_slice_native)."""
-    bl = _lib.BANDLIMIT[bandlimit] if not isinstance(bandlimit, int) else bandlimit
+    bl = _bandlimit(bandlimit)
     wl, sp, zs = list(map(float, wavelengths)), tuple(map(float, spacing)), list(map(float, zs))
     outs = [_AsmSliceFunction.apply(data, wl, sp, zs[k:k + _lib.THZ_MAX_Z], int(row), int(pad_h), int(pad_w),
                                     bool(unpad), bl) for k in range(0, len(zs), _lib.THZ_MAX_Z)]
@@ -217,25 +222,18 @@ def asm_propagate_zx(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad=Tr
 def _asm64_apply(data, wavelengths, spacing, zs, pad_h, pad_w, unpad, bandlimit, adjoint=False, out=None):
     """complex128 ASM (thz_asm64_forward): the same shapes as asm_apply; the fp64 adjoint runs one
     launch per plane and sums them."""
-    L = _lib.lib()
     data = data.contiguous()
+    field, out_shape = _asm_shapes(data, zs, pad_h, pad_w, unpad, adjoint)
     if adjoint:
-        Z, B, C, Ho, Wo = data.shape
-        if Z != len(zs):
-            raise ValueError(f"adjoint: {Z} gradient planes for {len(zs)} z values")
-        H = Ho - (0 if unpad else 2 * pad_h)
-        W = Wo - (0 if unpad else 2 * pad_w)
         res = None
         for k, z in enumerate(zs):
-            gk = _asm64_launch(data[k:k + 1], (B, C, H, W), wavelengths, spacing, [z], pad_h, pad_w, unpad, bandlimit,
-                               True, torch.empty((B, C, H, W), dtype=torch.complex128, device=data.device))
+            gk = _asm64_launch(data[k:k + 1], field, wavelengths, spacing, [z], pad_h, pad_w, unpad, bandlimit,
+                               True, torch.empty(field, dtype=torch.complex128, device=data.device))
             res = gk if res is None else res + gk
         return res
-    B, C, H, W = data.shape
-    Ho, Wo = (H, W) if unpad else (H + 2 * pad_h, W + 2 * pad_w)
     if out is None:
-        out = torch.empty((len(zs), B, C, Ho, Wo), dtype=torch.complex128, device=data.device)
-    return _asm64_launch(data, (B, C, H, W), wavelengths, spacing, zs, pad_h, pad_w, unpad, bandlimit, False, out)
+        out = torch.empty(out_shape, dtype=torch.complex128, device=data.device)
+    return _asm64_launch(data, field, wavelengths, spacing, zs, pad_h, pad_w, unpad, bandlimit, False, out)
 
 
 def _asm64_launch(data, shape, wavelengths, spacing, zs, pad_h, pad_w, unpad, bandlimit, adjoint, out):
@@ -247,13 +245,7 @@ def _asm64_launch(data, shape, wavelengths, spacing, zs, pad_h, pad_w, unpad, ba
                        Z=len(zs), adjoint=int(adjoint), dx=float(spacing[0]), dy=float(spacing[1]),
                        wavelengths=ctypes.cast(wl, ctypes.POINTER(ctypes.c_double)),
                        z=ctypes.cast(zv, ctypes.POINTER(ctypes.c_double)))
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.thz_asm64_workspace_size(ctypes.byref(d), ctypes.byref(nbytes)))
-    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=data.device)
-    with torch.cuda.device(data.device):
-        _lib.check(L.thz_asm64_forward(ctypes.byref(d), ctypes.c_void_p(data.data_ptr()),
-                                       ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                       ctypes.c_size_t(ws.numel()), _stream_handle()))
+    _launch(L.thz_asm64_workspace_size, L.thz_asm64_forward, d, data.device, data, out)
     return out
 
 
@@ -293,7 +285,7 @@ def asm_transfer_function(wavelengths, spacing, z, H, W, pad_h, pad_w, bandlimit
     if dev.type != "cuda":
         raise RuntimeError(f"ASM transfer function: the MI355X path needs a ROCm device (got {dev}); "
                            "this framework has no CPU compute path")
-    bl = _lib.BANDLIMIT[bandlimit] if not isinstance(bandlimit, int) else bandlimit
+    bl = _bandlimit(bandlimit)
     d = _asm_desc(1, len(wavelengths), int(H), int(W), int(pad_h), int(pad_w), True, bl, wavelengths, spacing,
                   [float(z)], False)
     out = torch.empty((1, len(wavelengths), H + 2 * pad_h, W + 2 * pad_w), dtype=torch.complex64, device=dev)
@@ -326,7 +318,7 @@ def asm_propagate(data, wavelengths, spacing, zs, pad_h, pad_w, unpad=True, band
     """Differentiable ASM over Z planes: [B,C,H,W] -> [Z,B,C,Ho,Wo] (HIP kernels); ``mask``: an
     aperture folded onto the output (window_mask_fusable geometry only); ``z_dev``: the planes in
     device memory (_asm_desc)."""
-    bl = _lib.BANDLIMIT[bandlimit] if not isinstance(bandlimit, int) else bandlimit
+    bl = _bandlimit(bandlimit)
     return _AsmFunction.apply(data, list(map(float, wavelengths)), tuple(map(float, spacing)),
                               list(map(float, zs)), int(pad_h), int(pad_w), bool(unpad), bl, int(z_chunk), mask, z_dev)
 
@@ -350,18 +342,10 @@ class _AsmModulatedFunction(torch.autograd.Function):
                       z_dev=z_dev)
         m = pend.desc()
         L = _lib.lib()
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(L.thz_asm_workspace_size(ctypes.byref(d), ctypes.byref(nbytes)))
-        ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=field.device)
         out = torch.empty((len(zs), B, C, Ho, Wo), dtype=torch.complex64, device=field.device)
         hfull = torch.empty((H, W), dtype=torch.float32, device=field.device)
-        noise = pend.noise
-        with torch.cuda.device(field.device):
-            _lib.check(L.thz_asm_forward_modulated(
-                ctypes.byref(d), ctypes.byref(m), ctypes.c_void_p(field.data_ptr()), ctypes.c_void_p(h.data_ptr()),
-                ctypes.c_void_p(noise.data_ptr() if noise is not None else 0), ctypes.c_void_p(hfull.data_ptr()),
-                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
-                _stream_handle()))
+        _launch(L.thz_asm_workspace_size, L.thz_asm_forward_modulated, d, field.device, ctypes.byref(m), field, h,
+                pend.noise, hfull, out)
         if pend.hfull is None:
             pend.hfull = hfull
         ctx.save_for_backward(field, h)
@@ -407,7 +391,7 @@ def asm_propagate_modulated(pend, wavelengths, spacing, zs, pad_h, pad_w, unpad=
                             z_dev=None):
     """Differentiable fused DOE modulation + ASM over Z planes: [B,C,H,W] -> [Z,B,C,Ho,Wo]; ``mask``
     and ``z_dev`` as asm_propagate."""
-    bl = _lib.BANDLIMIT[bandlimit] if not isinstance(bandlimit, int) else bandlimit
+    bl = _bandlimit(bandlimit)
     height, weight = _doe_inputs(pend)
     return _AsmModulatedFunction.apply(pend.field, height, weight, pend, list(map(float, wavelengths)),
                                        tuple(map(float, spacing)), list(map(float, zs)), int(pad_h), int(pad_w),
@@ -442,10 +426,7 @@ class _AsmLossFunction(torch.autograd.Function):
         d = _asm_desc(B, C, H, W, pad_h, pad_w, unpad, bandlimit, wavelengths, spacing, zs, False, z_dev=z_dev)
         ld = _lib.LossDesc(B=Z * B, C=C, H=Ho, W=Wo, tB=t4.shape[0], tC=t4.shape[1])
         L = _lib.lib()
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(L.thz_asm_workspace_size(ctypes.byref(d), ctypes.byref(nbytes)))
         dev = field.device
-        ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=dev)
         out = torch.empty((Z, B, C, Ho, Wo), dtype=torch.complex64, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         stats = torch.empty(L.thz_intensity_mse_workspace_size(ctypes.byref(ld)) // 4, dtype=torch.float32,
@@ -457,15 +438,8 @@ class _AsmLossFunction(torch.autograd.Function):
             hfull = torch.empty((H, W), dtype=torch.float32, device=dev)
             noise = pend.noise
             m = pend.desc()
-
-        def ptr(t):
-            return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-        with torch.cuda.device(dev):
-            _lib.check(L.thz_asm_forward_loss(
-                ctypes.byref(d), ctypes.byref(m) if m is not None else None, ptr(field), ptr(h), ptr(noise),
-                ptr(hfull), ctypes.byref(ld), ptr(t4), ptr(out), ptr(loss), ptr(stats), ptr(ws),
-                ctypes.c_size_t(ws.numel()), _stream_handle()))
+        _launch(L.thz_asm_workspace_size, L.thz_asm_forward_loss, d, dev, ctypes.byref(m) if m is not None else None,
+                field, h, noise, hfull, ctypes.byref(ld), t4, out, loss, stats)
         if pend is not None and pend.hfull is None:
             pend.hfull = hfull
         ctx.save_for_backward(field, h, out, t4, stats)
@@ -490,18 +464,11 @@ class _AsmLossFunction(torch.autograd.Function):
             ld = _lib.LossDesc(B=len(zs) * B, C=C, H=Ho, W=Wo, tB=tB, tC=tC)
             d = _asm_desc(B, C, H, W, pad_h, pad_w, unpad, bandlimit, wavelengths, spacing, zs, True, z_dev=z_dev)
             L = _lib.lib()
-            nbytes = ctypes.c_size_t(0)
-            _lib.check(L.thz_asm_workspace_size(ctypes.byref(d), ctypes.byref(nbytes)))
-            ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=out.device)
             gm = torch.empty((B, C, H, W), dtype=torch.complex64, device=out.device)
             g = g_loss.detach().float().contiguous()
             go = g_out.contiguous() if g_out is not None else None
-            with torch.cuda.device(out.device):
-                _lib.check(L.thz_asm_adjoint_loss(
-                    ctypes.byref(d), ctypes.byref(ld), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(t4.data_ptr()),
-                    ctypes.c_void_p(stats.data_ptr()), ctypes.c_void_p(g.data_ptr()),
-                    ctypes.c_void_p(go.data_ptr() if go is not None else 0), ctypes.c_void_p(gm.data_ptr()),
-                    ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream_handle()))
+            _launch(L.thz_asm_workspace_size, L.thz_asm_adjoint_loss, d, out.device, ctypes.byref(ld), out, t4, stats,
+                    g, go, gm)
         gh = gw = None
         pend = ctx.pend
         if pend is None:
@@ -518,7 +485,7 @@ def asm_propagate_loss(x, target, wavelengths, spacing, z, pad_h, pad_w, unpad=T
     broadcast over the Z B plane-major items); ``z_dev`` as asm_propagate.  ``pend``
     (doe.PendingModulation, not yet formed): propagate its modulation of ``pend.field`` (``x`` is
     then ignored), as asm_propagate_modulated."""
-    bl = _lib.BANDLIMIT[bandlimit] if not isinstance(bandlimit, int) else bandlimit
+    bl = _bandlimit(bandlimit)
     zs = [float(v) for v in z] if isinstance(z, (list, tuple)) else [float(z)]
     if len(zs) > _lib.THZ_MAX_Z:
         raise ValueError(f"the fused loss takes at most {_lib.THZ_MAX_Z} planes per call")
@@ -569,6 +536,17 @@ def fft_rows(x, inverse=False):
     return out
 
 
+def _by_dtype(tag, dtype):
+    """(descriptor class, host array maker, ctypes scalar, size_fn, run_fn) of the propagator ``tag``
+    ("czt" / "rsc") in the field's precision: the fp64 entries for complex128, else the fp32 ones."""
+    L = _lib.lib()
+    if dtype == torch.complex128:
+        return (getattr(_lib, f"{tag.capitalize()}Desc64"), _lib.double_array, ctypes.c_double,
+                getattr(L, f"thz_{tag}64_workspace_size"), getattr(L, f"thz_{tag}64_forward"))
+    return (getattr(_lib, f"{tag.capitalize()}Desc"), _lib.float_array, ctypes.c_float,
+            getattr(L, f"thz_{tag}_workspace_size"), getattr(L, f"thz_{tag}_forward"))
+
+
 def czt_apply(data, wavelengths, spacing, z, outH, outW, odx, ody, adjoint=False, field_hw=None):
     """Chirp-z propagation [B,C,H,W] -> [B,C,outW,outH] (Props/CZT_Prop.py:252-314) on the HIP kernels.
 
@@ -576,33 +554,19 @@ def czt_apply(data, wavelengths, spacing, z, outH, outW, odx, ody, adjoint=False
     _require_device(data, "CZT")
     if data.dtype not in (torch.complex64, torch.complex128):
         raise TypeError(f"CZT kernels compute in complex64 or complex128; got {data.dtype}")
-    f64 = data.dtype == torch.complex128
     data = data.contiguous()
     B, C = data.shape[:2]
     H, W = (int(v) for v in (field_hw if adjoint else data.shape[-2:]))
     if adjoint and tuple(data.shape[-2:]) != (int(outW), int(outH)):
         raise ValueError(f"CZT adjoint: gradient {tuple(data.shape)} is not [B, C, outW, outH]")
-    if f64:
-        wl = _lib.double_array(wavelengths)
-        d = _lib.CztDesc64(B=B, C=C, H=H, W=W, outH=int(outH), outW=int(outW), dx=float(spacing[0]),
-                           dy=float(spacing[1]), odx=float(odx), ody=float(ody), z=float(z),
-                           wavelengths=ctypes.cast(wl, ctypes.POINTER(ctypes.c_double)), adjoint=int(bool(adjoint)))
-    else:
-        wl = _lib.float_array(wavelengths)
-        d = _lib.CztDesc(B=B, C=C, H=H, W=W, outH=int(outH), outW=int(outW), dx=float(spacing[0]),
-                         dy=float(spacing[1]), odx=float(odx), ody=float(ody), z=float(z),
-                         wavelengths=ctypes.cast(wl, ctypes.POINTER(ctypes.c_float)), adjoint=int(bool(adjoint)))
-    L = _lib.lib()
-    size_fn, run_fn = (L.thz_czt64_workspace_size, L.thz_czt64_forward) if f64 else \
-        (L.thz_czt_workspace_size, L.thz_czt_forward)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(size_fn(ctypes.byref(d), ctypes.byref(nbytes)))
-    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=data.device)
+    desc, array, ctype, size_fn, run_fn = _by_dtype("czt", data.dtype)
+    wl = array(wavelengths)
+    d = desc(B=B, C=C, H=H, W=W, outH=int(outH), outW=int(outW), dx=float(spacing[0]), dy=float(spacing[1]),
+             odx=float(odx), ody=float(ody), z=float(z), wavelengths=ctypes.cast(wl, ctypes.POINTER(ctype)),
+             adjoint=int(bool(adjoint)))
     oshape = (B, C, H, W) if adjoint else (B, C, int(outW), int(outH))
     out = torch.empty(oshape, dtype=data.dtype, device=data.device)
-    with torch.cuda.device(data.device):
-        _lib.check(run_fn(ctypes.byref(d), ctypes.c_void_p(data.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                          ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream_handle()))
+    _launch(size_fn, run_fn, d, data.device, data, out)
     return out
 
 
@@ -616,26 +580,13 @@ def rsc_apply(data, wavelengths, spacing, z, vectorial=False, adjoint=False, fie
     _require_device(data, "RSC")
     if data.dtype not in (torch.complex64, torch.complex128):
         raise TypeError(f"RSC kernels compute in complex64 or complex128; got {data.dtype}")
-    f64 = data.dtype == torch.complex128
     data = data.contiguous()
     B, C = data.shape[:2]
     H, W = field_hw if adjoint else data.shape[-2:]
-    if f64:
-        wl = _lib.double_array(wavelengths)
-        d = _lib.RscDesc64(B=B, C=C, H=int(H), W=int(W), vectorial=int(bool(vectorial)), dx=float(spacing[0]),
-                           dy=float(spacing[1]), z=float(z),
-                           wavelengths=ctypes.cast(wl, ctypes.POINTER(ctypes.c_double)), adjoint=int(bool(adjoint)))
-    else:
-        wl = _lib.float_array(wavelengths)
-        d = _lib.RscDesc(B=B, C=C, H=int(H), W=int(W), vectorial=int(bool(vectorial)), dx=float(spacing[0]),
-                         dy=float(spacing[1]), z=float(z), wavelengths=ctypes.cast(wl, ctypes.POINTER(ctypes.c_float)),
-                         adjoint=int(bool(adjoint)))
-    L = _lib.lib()
-    size_fn, run_fn = (L.thz_rsc64_workspace_size, L.thz_rsc64_forward) if f64 else \
-        (L.thz_rsc_workspace_size, L.thz_rsc_forward)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(size_fn(ctypes.byref(d), ctypes.byref(nbytes)))
-    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=data.device)
+    desc, array, ctype, size_fn, run_fn = _by_dtype("rsc", data.dtype)
+    wl = array(wavelengths)
+    d = desc(B=B, C=C, H=int(H), W=int(W), vectorial=int(bool(vectorial)), dx=float(spacing[0]), dy=float(spacing[1]),
+             z=float(z), wavelengths=ctypes.cast(wl, ctypes.POINTER(ctype)), adjoint=int(bool(adjoint)))
     if adjoint:
         if tuple(data.shape[-2:]) != (2 * (H // 2), 2 * (W // 2)):
             raise ValueError(f"RSC adjoint: gradient {tuple(data.shape)} does not match field {(H, W)}")
@@ -647,7 +598,5 @@ def rsc_apply(data, wavelengths, spacing, z, vectorial=False, adjoint=False, fie
         # H or W = 1: the reference's [..., H:, W:] window is empty (Props/RSC_Prop.py:203-207; run
         # here: [B, C, 0, 2 (W // 2)] and the like); the adjoint of an empty output is zero
         return out.zero_()
-    with torch.cuda.device(data.device):
-        _lib.check(run_fn(ctypes.byref(d), ctypes.c_void_p(data.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                          ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream_handle()))
+    _launch(size_fn, run_fn, d, data.device, data, out)
     return out
