@@ -749,7 +749,9 @@ __device__ __forceinline__ void asm_cols_body(const float2* __restrict__ T, floa
         // streaming stores here ran K2 4.1 -> 13.8 ms)
         if ((unsigned)r < (unsigned)a.Hout) dst[u_roff(r)] = v;
       };
-      fft_pow2_io<true, PN, TT, FFT_TAIL, false, false>(lds, twl, tz, ld1, sv1);
+      // mid0: stage 0 skips the zero operands' half of its butterfly too (both forms; the
+      // recurrence's D slots are never read by it); one scalar branch around stage 0 only
+      fft_pow2_io<true, PN, TT, FFT_TAIL, false, false>(lds, twl, tz, ld1, sv1, RL == 16 && mid0);
     }
   } else {
     if constexpr (ZSUM) {
@@ -1104,6 +1106,9 @@ __device__ __forceinline__ void rows_inv_body(const float2* __restrict__ U, floa
       const int w = j - (MID ? PN / 4 : a.out_c0);
       if ((unsigned)w < (unsigned)(MID ? PN / 2 : a.Wout)) put(w, v);
     };
+    // (the stage itself stays the full butterfly on those zeros: dft16's MID_IN form, which the column
+    // pass takes on its own mid0, ran this gather-latency-bound pass 4.250 -> 4.300 ms at cfg2 with 32
+    // VALU fewer per thread)
     fft_pow2_run<true, PN, TT, FFT_ROWS>(lds, twl, tid, ld, sv, tw_hook);
   } else {
     for (int j = tid; j < a.Pw; j += nt) {

@@ -130,8 +130,13 @@ __device__ __forceinline__ void dft8(float2* v) {
 
 // HALF_IN: inputs 8..15 are zero (a zero-padded half transform's first stage), so the first DFT4
 // layer is two-input.
-template <bool INV, bool HALF_IN = false>
+// MID_IN: inputs 4..11 are absent (zero, never read: a band-limited spectrum's first inverse stage,
+// whose operands 4..11 are the frequencies N/4 <= |m| < 3N/4).  Each first-layer DFT4 sees
+// (a0, 0, 0, a3) and keeps dft4's surviving sums in dft4's order, so for finite data the outputs are
+// those of the full butterfly on explicit zeros bit for bit, up to the sign of a zero.
+template <bool INV, bool HALF_IN = false, bool MID_IN = false>
 __device__ __forceinline__ void dft16(float2* v) {
+  static_assert(!(HALF_IN && MID_IN), "one pruned form at a time");
   // 16 = 4 x 4: B[r2][q1] = DFT4_{r1}(v[r2 + 4 r1]); B *= w16^(r2 q1); y[q1 + 4 q2] = DFT4_{r2}(B[.][q1])
   float2 b[4][4];
 #pragma unroll
@@ -142,6 +147,13 @@ __device__ __forceinline__ void dft16(float2* v) {
       b[r2][2] = csub(a0, a1);
       b[r2][1] = add_mi<INV>(a0, a1);
       b[r2][3] = sub_mi<INV>(a0, a1);
+    } else if constexpr (MID_IN) {
+      // dft4 with a1 = a2 = 0: t0 = t1 = a0, t2 = a3, d = -a3
+      const float2 a0 = v[r2], a3 = v[r2 + 12];
+      b[r2][0] = cadd(a0, a3);
+      b[r2][2] = csub(a0, a3);
+      b[r2][1] = sub_mi<INV>(a0, a3);
+      b[r2][3] = add_mi<INV>(a0, a3);
     } else {
       b[r2][0] = v[r2];
       b[r2][1] = v[r2 + 4];
@@ -454,7 +466,7 @@ __device__ __forceinline__ int stage_order(int tid) {
 
 template <int R, bool INV, int N, int L, int T, bool IN_LDS, bool OUT_LDS, int LIN = 1, int LOUT = L, class Tw,
           class Ld, class Sv>
-__device__ __forceinline__ void stage_x(float2* lds, const Tw& tw, int tid, Ld& ld, Sv& sv) {
+__device__ __forceinline__ void stage_x(float2* lds, const Tw& tw, int tid, Ld& ld, Sv& sv, bool mid0 = false) {
   constexpr int NB = N / R;
   constexpr int MB = NB / T;  // butterflies per thread (exact)
   static_assert(MB * T == NB, "pow2 plan must tile exactly");
@@ -470,6 +482,17 @@ __device__ __forceinline__ void stage_x(float2* lds, const Tw& tw, int tid, Ld& 
 #pragma unroll
       for (int r = 0; r < R; ++r) v[m][r] = src[c64_lay<LIN>(m * T + r * NB) - c64_lay<LIN>(m * T)];
     } else {
+      if constexpr (R == 16 && L == 1) {
+        // mid0 (wave-uniform): operands 4..11 are zero for the whole wave -- neither loaded nor
+        // transformed (dft16's MID_IN form); the results land in the same v[m][0..15]
+        if (mid0) {
+#pragma unroll
+          for (int r = 0; r < R; ++r)
+            if (r < 4 || r >= 12) v[m][r] = ld(m, r, i + r * NB);
+          dft16<INV, false, true>(v[m]);
+          continue;
+        }
+      }
 #pragma unroll
       for (int r = 0; r < R; ++r) v[m][r] = ld(m, r, i + r * NB);
     }
@@ -686,9 +709,13 @@ struct NoIO {
 
 // Stages S .. NST-1 of a power-of-two transform.  Stage 0 reads through ld unless
 // FIRST_LDS; the final stage writes through sv unless LAST_LDS.
+// mid0 (wave-uniform; a radix-16 stage 0 reading through ld): this wave's first-stage operands
+// 4..11 are all zero, so ld is not called for them and stage 0 runs dft16's MID_IN form.  Only
+// stage 0's arithmetic differs: every later stage, exchange and store is the same code.
 template <bool INV, int N, int T, int MODE, bool FIRST_LDS, bool LAST_LDS, int S = 0, int L = 1, class Tw, class Ld,
           class Sv>
-__device__ __forceinline__ void fft_pow2_io(float2* lds, const Tw& tw, int tid, Ld& ld, Sv& sv) {
+__device__ __forceinline__ void fft_pow2_io(float2* lds, const Tw& tw, int tid, Ld& ld, Sv& sv,
+                                            bool mid0 = false) {
   using P = Pow2Sched<N>;
   constexpr int NS = P::nst(MODE);
   if constexpr (S < NS) {
@@ -709,7 +736,7 @@ __device__ __forceinline__ void fft_pow2_io(float2* lds, const Tw& tw, int tid, 
       for (int s = 0; s < 16; ++s) x[s] = src[c64_lay<LIN>(2 * s * LP) - c64_lay<LIN>(0)];
       stage_r32_pair_last<INV, N>(tw, tid, x, sv);
     } else {
-      stage_x<R, INV, N, L, T, IN_LDS, OUT_LDS, LIN, LOUT>(lds, tw, tid, ld, sv);
+      stage_x<R, INV, N, L, T, IN_LDS, OUT_LDS, LIN, LOUT>(lds, tw, tid, ld, sv, S == 0 && mid0);
       fft_pow2_io<INV, N, T, MODE, FIRST_LDS, LAST_LDS, S + 1, L * R>(lds, tw, tid, ld, sv);
     }
   }
