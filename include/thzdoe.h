@@ -55,7 +55,8 @@ typedef void* thz_stream_t; /* hipStream_t */
  * 7 added thz_doe_quant_backward and thz_radial_quant_backward, 8 thz_step_fetch and
  * thz_adam_step, 9 thz_asm_slice_workspace_size and thz_asm_slice_forward;
  * thz_asm_slice_adjoint_workspace_size and thz_asm_slice_adjoint (library 0.6.0) changed no struct and
- * are purely additive, so the version stays 9 -- a caller detects them by symbol):
+ * are purely additive, so the version stays 9 -- a caller detects them by symbol; likewise
+ * thz_czt_slice_workspace_size and thz_czt_slice_forward with their own new thz_czt_slice_desc):
  * a caller compares thz_abi_version()
  * with the THZ_ABI_VERSION it was compiled against before its first call, since a shorter
  * struct from an older header would make the library read past it.  Descriptors are plain C
@@ -192,6 +193,44 @@ typedef struct thz_czt_desc {
 int thz_czt_workspace_size(const thz_czt_desc* d, size_t* bytes);
 int thz_czt_forward(const thz_czt_desc* d, const void* in, void* out, void* workspace, size_t workspace_bytes,
                     thz_stream_t stream);
+
+/*
+ * CZT z-x slice: one zoomed output row of every plane of a z-sweep, without forming the planes --
+ * the x-z cross-section of a focal region on the zoomed grid (Props/CZT_Prop.py:227-314 called once
+ * per plane, keeping out[..., row, :]; :260-262 "useful for imaging light in the focal plane: allows
+ * high resolution zoom").  Purely additive (no struct changed): THZ_ABI_VERSION stays 9, a caller
+ * detects the entries by symbol.
+ *   in [B, C, H, W] -> out [Z, B, C, outH] == thz_czt_forward(z = z[k])'s out[:, :, row, :] for every k
+ * row is the p of out[b, c, p, q], 0 <= row < outW.  For a fixed p the pass along H is a dot product
+ * per input column: a collapse kernel forms S_k[b,c,w] = sum_h in[b,c,h,w] F_{z_k,c}(x_h, y_w)
+ * preB[h] gB[p + H - h] for four planes per read of the field, then one W-axis Bluestein line of
+ * np2 = 2^ceil(log2(W + outH - 1)) points per (k, b, c).  No intermediate of a plane's size, no
+ * second pass, no per-z table cache; two calls with the same inputs are bit-identical (H is split in
+ * a fixed way and its partial sums are added in order, no atomics).  Forward only, host z[] only.
+ * Validation, all before any device call: the shape rules of thz_czt_forward (square output,
+ * C <= THZ_MAX_WAVELENGTHS, THZ_E_ARG for a power-of-two Bluestein length, THZ_E_UNSUPPORTED past the
+ * longest transform); a bad row, Z outside 1 .. THZ_MAX_Z or a null pointer THZ_E_ARG; a short or
+ * null workspace THZ_E_WORKSPACE (the message names the size).
+ * Workspace, with zc = min(Z, 16) planes per chunk and r32(n) = n rounded up to 32:
+ *   8 zc C (r32(W) + r32(outH) + np2 + r32(H) + 32)     tables per (plane, wavelength)
+ * + 8 hs zc B C W                                        S, in hs <= 8 partial sums over H
+ * bytes, each part rounded up to 256 -- nothing of size H x outH or outW x outH, and no growth with
+ * Z past one chunk.
+ */
+typedef struct thz_czt_slice_desc {
+  int B, C, H, W;
+  int outH, outW;
+  float dx, dy, odx, ody;
+  int Z;                    /* 1 .. THZ_MAX_Z */
+  const float* z;           /* host [Z] */
+  const float* wavelengths; /* host [C] */
+  int row;                  /* 0 <= row < outW: the p of out[b, c, p, q] */
+} thz_czt_slice_desc;
+
+int thz_czt_slice_workspace_size(const thz_czt_slice_desc* d, size_t* bytes);
+int thz_czt_slice_forward(const thz_czt_slice_desc* d, const void* in /* [B,C,H,W] */,
+                          void* out /* [Z,B,C,outH] */, void* workspace, size_t workspace_bytes,
+                          thz_stream_t stream);
 
 /*
  * Rayleigh-Sommerfeld convolution, Props/RSC_Prop.py:170-215 (RSC_prop.forward), and its
@@ -532,7 +571,8 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * thz_timing_read() synchronises on the pending events and returns the summed
  * duration and launch count for one kernel name ("asm_rows_fwd", "asm_cols", "asm_rows_inv"; the
  * z-x slice: "asm_rows_fwd", "asm_cols_slice", "asm_rows_slice"; its adjoint: "asm_rows_fwd",
- * "asm_cols_slice_adj", "asm_rows_inv"; ...).
+ * "asm_cols_slice_adj", "asm_rows_inv"; the CZT z-x slice: "czt_slice_tables", "czt_slice_collapse",
+ * "czt_slice_line"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

@@ -27,6 +27,16 @@ def _pow2(n):
     return n > 0 and n & (n - 1) == 0
 
 
+def _z_host(z):
+    """The plane distances of a z-sweep as host floats (a tensor, a sequence or one value)."""
+    if torch.is_tensor(z):
+        return [float(v) for v in z.detach().reshape(-1).cpu().tolist()]
+    try:
+        return [_f(v) for v in z]
+    except TypeError:
+        return [float(z)]
+
+
 class CZT_prop(nn.Module):
     def __init__(self, z_distance: float = 0.0, device: str = None) -> None:
         super().__init__()
@@ -88,16 +98,7 @@ class CZT_prop(nn.Module):
         ody = sp[1] if outputPixel_dy is None else _f(outputPixel_dy)
         data = field.data
         x = _prop.kernel_dtype(data, "CZT_prop", field.wavelengths)
-        if outputHeight == outputWidth == 1 and _pow2(W) and not _pow2(H):
-            # the reference's second Bluestein pass (m = W, M = 1) has np2 = mp = W: its kept
-            # slice b[W:W+1] is empty and it returns a [B, C, 1, 0] field (Props/CZT_Prop.py:206,211;
-            # run here).  Every other power-of-two Bluestein length raises there, and the library
-            # refuses it (THZ_E_ARG -> RuntimeError).
-            # (kept in the autograd graph as the reference's slice is: a zero gradient flows back)
-            out = x.new_zeros(x.shape[0], x.shape[1], 1, 0) + 0 * x.sum((-2, -1), keepdim=True)[..., :0]
-        else:
-            out = _CztFunction.apply(x, tuple(field.wavelengths_host), tuple(sp), self._zh, outputHeight,
-                                     outputWidth, odx, ody)
+        out = self._plane(x, field, self._zh, outputHeight, outputWidth, odx, ody)
         sp_out = [outputPixel_dx if outputPixel_dx is not None else field.spacing[0],
                   outputPixel_dy if outputPixel_dy is not None else field.spacing[1]]
         if all(torch.is_tensor(v) for v in sp_out):
@@ -105,6 +106,102 @@ class CZT_prop(nn.Module):
         else:
             sp_out = [_f(v) for v in sp_out]
         return ElectricField(data=out, wavelengths=field.wavelengths, spacing=sp_out, device=field.device)
+
+    @staticmethod
+    def _empty_plane(H, W, outputHeight, outputWidth):
+        """The one geometry whose reference result is an empty [B, C, 1, 0] field (see _plane)."""
+        return outputHeight == outputWidth == 1 and _pow2(W) and not _pow2(H)
+
+    def _plane(self, x, field, zh, outputHeight, outputWidth, odx, ody):
+        """One plane [B, C, outW, outH] of the kernel-precision data ``x`` at the host distance ``zh``."""
+        if self._empty_plane(field.height, field.width, outputHeight, outputWidth):
+            # the reference's second Bluestein pass (m = W, M = 1) has np2 = mp = W: its kept
+            # slice b[W:W+1] is empty and it returns a [B, C, 1, 0] field (Props/CZT_Prop.py:206,211;
+            # run here).  Every other power-of-two Bluestein length raises there, and the library
+            # refuses it (THZ_E_ARG -> RuntimeError).
+            # (kept in the autograd graph as the reference's slice is: a zero gradient flows back)
+            return x.new_zeros(x.shape[0], x.shape[1], 1, 0) + 0 * x.sum((-2, -1), keepdim=True)[..., :0]
+        return _CztFunction.apply(x, tuple(field.wavelengths_host), tuple(field.spacing_host), zh, outputHeight,
+                                  outputWidth, odx, ody)
+
+    @staticmethod
+    def _out_grid(field, outputHeight, outputWidth, outputPixel_dx, outputPixel_dy):
+        """forward's defaults: the output grid is the input grid (Props/CZT_Prop.py:280-290)."""
+        sp = field.spacing_host
+        return (field.height if outputHeight is None else int(outputHeight),
+                field.width if outputWidth is None else int(outputWidth),
+                sp[0] if outputPixel_dx is None else _f(outputPixel_dx),
+                sp[1] if outputPixel_dy is None else _f(outputPixel_dy))
+
+    def propagate_planes(self, field: ElectricField, z_list, outputHeight=None, outputWidth=None,
+                         outputPixel_dx=None, outputPixel_dy=None) -> torch.Tensor:
+        """Additive API: the planes of ``z_list`` -> [Z, B, C, outW, outH], ``forward`` per plane (the
+        same kernels, differentiable) stacked; the instance's own ``z`` is not touched.  The counterpart
+        of ASM_prop.propagate_planes, and the fallback and yardstick of propagate_zx."""
+        outH, outW, odx, ody = self._out_grid(field, outputHeight, outputWidth, outputPixel_dx, outputPixel_dy)
+        x = _prop.kernel_dtype(field.data, "CZT_prop", field.wavelengths)
+        return torch.stack([self._plane(x, field, zh, outH, outW, odx, ody) for zh in _z_host(z_list)])
+
+    def propagate_zx(self, field: ElectricField, z_list, row=None, axis="x", outputHeight=None, outputWidth=None,
+                     outputPixel_dx=None, outputPixel_dy=None) -> torch.Tensor:
+        """Additive API: one zoomed output row of every plane of ``z_list`` -> [Z, B, C, outH], equal to
+        ``propagate_planes(field, z_list, ...)[..., row, :]`` -- the x-z cross-section of a focal region
+        on the zoomed grid (Props/CZT_Prop.py:260-262: "useful for imaging light in the focal plane:
+        allows high resolution zoom"), which otherwise costs one ``forward`` per plane.  ``row`` is the
+        p of the [B, C, outW, outH] result's out[b, c, p, q]; None is the centre row outW // 2.
+        ``axis="y"`` returns ``planes[..., :, row]`` instead, [Z, B, C, outW].  ``z_list`` may have any
+        length (chunks of THZ_MAX_Z planes).
+
+        A complex64 device field that does not require grad (or under ``no_grad``) runs the slice
+        kernels (thz_czt_slice_forward): one streaming read of the field per four planes, one
+        Bluestein line per (z, b, c), nothing of a plane's size per z.  ``axis="y"`` runs them on the
+        transposed field with H / W, dx / dy and the output pixels exchanged, but only when
+        ``dx == dy``: the reference takes Dm = lambda z / dx from dx on BOTH axes
+        (Props/CZT_Prop.py:109-116), so the exchange is exact only then.  Every other input -- a
+        complex128 field, an input that requires grad, ``axis="y"`` with dx != dy, a geometry the
+        slice entry refuses as unsupported -- propagates the full planes in z-chunks whose temporary
+        stays under 10 GiB and slices each chunk, differentiably.  Geometries ``forward`` refuses
+        (a non-square output, a power-of-two Bluestein length) raise as it does; the one empty
+        [B, C, 1, 0] geometry of ``forward`` gives the correspondingly empty slice."""
+        if axis not in ("x", "y"):
+            raise ValueError(f"propagate_zx: axis must be 'x' or 'y', got {axis!r}")
+        outH, outW, odx, ody = self._out_grid(field, outputHeight, outputWidth, outputPixel_dx, outputPixel_dy)
+        n = outW if axis == "x" else outH
+        if row is None:
+            row = n // 2
+        row = int(row)
+        if not 0 <= row < n:
+            raise ValueError(f"propagate_zx: row {row} outside the valid range [0, {n}) of the output "
+                             f"{'rows' if axis == 'x' else 'columns'}")
+        zs = _z_host(z_list)
+        sp = tuple(field.spacing_host)
+        x = _prop.kernel_dtype(field.data, "CZT_prop", field.wavelengths)
+        B, C, H, W = x.shape
+        max_z = _prop._lib.THZ_MAX_Z
+        native = (x.dtype == torch.complex64 and x.is_cuda and not (torch.is_grad_enabled() and x.requires_grad)
+                  and not self._empty_plane(H, W, outH, outW) and (axis == "x" or sp[0] == sp[1]))
+        if native:
+            wl = tuple(field.wavelengths_host)
+            if axis == "y":
+                xs, geo = x.detach().transpose(-1, -2).contiguous(), ((sp[1], sp[0]), outW, outH, ody, odx)
+            else:
+                xs, geo = x.detach(), (sp, outH, outW, odx, ody)
+            out = torch.empty((len(zs), B, C, geo[1]), dtype=torch.complex64, device=x.device)
+            try:
+                for k in range(0, len(zs), max_z):
+                    _prop.czt_slice_apply(xs, wl, geo[0], zs[k:k + max_z], row, geo[1], geo[2], geo[3], geo[4],
+                                          out=out[k:k + max_z])
+                return out
+            except _prop._lib.ThzError as err:  # validated before any launch: nothing ran
+                if err.code != _prop._lib.THZ_E_UNSUPPORTED:
+                    raise
+        per_z = max(1, B * C * outW * outH * (16 if x.dtype == torch.complex128 else 8))
+        step = int(max(1, min(max_z, (10240 * 1024 * 1024) // per_z)))
+        outs = []
+        for k in range(0, len(zs), step):
+            planes = torch.stack([self._plane(x, field, zh, outH, outW, odx, ody) for zh in zs[k:k + step]])
+            outs.append(planes[..., row, :] if axis == "x" else planes[..., :, row])
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
 class _CztFunction(torch.autograd.Function):

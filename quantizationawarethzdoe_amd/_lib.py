@@ -32,6 +32,7 @@ EXPORTED = [
     "thz_asm_slice_workspace_size", "thz_asm_slice_forward",
     "thz_asm_slice_adjoint_workspace_size", "thz_asm_slice_adjoint",
     "thz_czt_workspace_size", "thz_czt_forward",
+    "thz_czt_slice_workspace_size", "thz_czt_slice_forward",
     "thz_rsc_workspace_size", "thz_rsc_forward",
     "thz_doe_modulate_forward", "thz_doe_modulate_backward", "thz_quant_forward", "thz_quant_backward",
     "thz_doe_quant_backward", "thz_radial_quant_backward",
@@ -74,6 +75,16 @@ class CztDesc(ctypes.Structure):
         ("outH", ctypes.c_int), ("outW", ctypes.c_int),
         ("dx", ctypes.c_float), ("dy", ctypes.c_float), ("odx", ctypes.c_float), ("ody", ctypes.c_float),
         ("z", ctypes.c_float), ("wavelengths", ctypes.POINTER(ctypes.c_float)), ("adjoint", ctypes.c_int),
+    ]
+
+
+class CztSliceDesc(ctypes.Structure):
+    _fields_ = [
+        ("B", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+        ("outH", ctypes.c_int), ("outW", ctypes.c_int),
+        ("dx", ctypes.c_float), ("dy", ctypes.c_float), ("odx", ctypes.c_float), ("ody", ctypes.c_float),
+        ("Z", ctypes.c_int), ("z", ctypes.POINTER(ctypes.c_float)),
+        ("wavelengths", ctypes.POINTER(ctypes.c_float)), ("row", ctypes.c_int),
     ]
 
 
@@ -232,6 +243,9 @@ def _declare(lib):
     lib.thz_radial_backward.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.thz_czt_workspace_size.argtypes = [ctypes.POINTER(CztDesc), ctypes.POINTER(c_size_t)]
     lib.thz_czt_forward.argtypes = [ctypes.POINTER(CztDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_czt_slice_workspace_size.argtypes = [ctypes.POINTER(CztSliceDesc), ctypes.POINTER(c_size_t)]
+    lib.thz_czt_slice_forward.argtypes = [ctypes.POINTER(CztSliceDesc), c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]
     lib.thz_gaussian_beam.argtypes = [ctypes.POINTER(GaussDesc), c_void_p, c_void_p]
     lib.thz_thin_lens.argtypes = [ctypes.POINTER(LensDesc), c_void_p, c_void_p, c_void_p]
     lib.thz_aperture.argtypes = [ctypes.POINTER(ApertureDesc), c_void_p, c_void_p, c_void_p]

@@ -821,6 +821,273 @@ static int czt_tables_for(const CztArgs& a, const thz_czt_desc* d, float2* ws, h
   return THZ_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// z-x slice: output row p of every plane of a z-sweep, out[k, b, c, q] = plane_k[b, c, p, q], without
+// the intermediate V and without pass B's transforms.  For a fixed p pass B (H axis) is one dot
+// product per input column, so with every table evaluated at Dm = lambda_c z_k / dx:
+//   coef_kc[h] = preB[h] gB[p + H - h]                      (gB[t] = 0 for t >= ntab, as in czt_tables)
+//   S_kbc[w]   = sum_h E[b,c,h,w] F_{z_k,c}(x_h, y_w) coef_kc[h]                  (czt_slice_collapse)
+//   out[k,b,c,q] = cst F0_{z_k,c}(x_out[p], y_out[q]) postB[p] BluesteinA(S_kbc)[q]   (czt_slice_line)
+// postB[p] = h_B[H-1+p] M_shift_B[p] without the 1/nrm of pass B's inverse transform (none runs);
+// pass A is the np2 form with its own 1/np2 in postA.  The planes go CZS_ZC at a time: per chunk one
+// table launch for every (k, c), one filter-spectrum FFT launch, one collapse, one line launch.
+// ---------------------------------------------------------------------------------------------
+constexpr int CZS_ZC = 16;      // planes per chunk (tables and S of one chunk live in the workspace)
+constexpr int CZS_ZT = 4;       // planes per thread of the collapse kernel: one field load serves 4 planes
+constexpr int CZS_HS_MAX = 8;   // at most this many splits of H (partial sums summed in order by the line kernel)
+constexpr int CZS_THREADS = 256;
+constexpr int CZS_WAVES = 8192;  // the collapse grid is split along H until it has about this many waves
+
+struct CztSliceArgs {
+  int BC, C, H, W, outH, outW, row;
+  int nz;          // planes of this chunk
+  int hs, hlen;    // splits of H and rows per split
+  float dx, dy, odx, ody;
+  BluePass pa, pb;  // both in the np2 form (pb only lends its m, M, ntab and frequency range)
+  // float2 offsets inside the table block of one (k, c); tabStride float2 per block
+  size_t preA, postA, ftA, coef, postB, tabStride;
+  float z[CZS_ZC];
+  float lam[THZ_MAX_WAVELENGTHS];
+};
+
+// pre / post / 1/h of pass A, coef and postB[p] of pass B for every (plane, wavelength) of a chunk
+__global__ void czt_slice_tables(CztSliceArgs a, float2* __restrict__ ws) {
+  const int kc = blockIdx.y, k = kc / a.C, c = kc - k * a.C;
+  float2* tab = ws + (size_t)kc * a.tabStride;
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  const double twopi = 6.283185307179586476925;
+  {
+    const BluePass& p = a.pa;
+    const BlueD b = blue_params(p, (double)a.lam[c], (double)a.z[k], (double)a.dx);
+    if (n < p.m) {
+      const double j = n;
+      tab[a.preA + n] = cis_d(-b.thA * j + b.thW * j * j / 2);
+    }
+    if (n < p.M) {
+      const double l = n;
+      const double ell = l / p.M * (b.D2 - b.D1) + b.D1;
+      const double shift = -twopi * ell * (-p.m / 2.0 + 0.5) / b.Dm;
+      const float2 v = cis_d(b.thW * l * l / 2 + shift);
+      const float s = 1.0f / (float)p.nrm;
+      tab[a.postA + n] = make_float2(v.x * s, v.y * s);
+    }
+    if (n < p.np2) {
+      if (n < p.ntab) {
+        const double jj = n - p.m + 1;
+        tab[a.ftA + n] = cis_d(-b.thW * jj * jj / 2);
+      } else {
+        tab[a.ftA + n] = make_float2(0.f, 0.f);
+      }
+    }
+  }
+  {
+    const BluePass& p = a.pb;
+    const BlueD b = blue_params(p, (double)a.lam[c], (double)a.z[k], (double)a.dx);
+    if (n < p.m) {
+      // preB[h] gB[t], t = row + m - h: one phase, -thA h + thW (h^2 - (t - m + 1)^2) / 2
+      const double h = n, jj = a.row - n + 1;
+      tab[a.coef + n] = a.row + p.m - n < p.ntab ? cis_d(-b.thA * h + b.thW * (h * h - jj * jj) / 2)
+                                                 : make_float2(0.f, 0.f);
+    }
+    if (n == 0) {
+      const double l = a.row;
+      const double ell = l / p.M * (b.D2 - b.D1) + b.D1;
+      const double shift = -twopi * ell * (-p.m / 2.0 + 0.5) / b.Dm;
+      tab[a.postB] = cis_d(b.thW * l * l / 2 + shift);
+    }
+  }
+}
+
+// S partial sums: P[hs][k][bc][w] = sum over the rows h of split hs of E[bc,h,w] F_k(x_h, y_w) coef_kc[h].
+// Lanes along w (coalesced streaming loads of a field row), a loop over h; each loaded element stays
+// in a register for the CZS_ZT planes of the thread, whose coef values are wave-uniform loads.  One RS
+// kernel evaluation per (element, plane): VALU / transcendental-bound, not bandwidth-bound.
+__global__ void __launch_bounds__(CZS_THREADS) czt_slice_collapse(const float2* __restrict__ in, float2* __restrict__ P,
+                                                                  const float2* __restrict__ ws, CztSliceArgs a) {
+  const int wb = (a.W + CZS_THREADS - 1) / CZS_THREADS, ng = (a.nz + CZS_ZT - 1) / CZS_ZT;
+  int id = blockIdx.x;
+  const int bw = id % wb;
+  id /= wb;
+  const int g = id % ng;
+  id /= ng;
+  const int hsi = id % a.hs, bc = id / a.hs;
+  const int w = bw * CZS_THREADS + (int)threadIdx.x;
+  if (w >= a.W) return;
+  const int c = bc % a.C;
+  const float lam = a.lam[c];
+  const float k = 6.283185307179586f / lam;
+  float zk[CZS_ZT];
+  RsPhase rph[CZS_ZT];
+  const float2* cf[CZS_ZT];
+#pragma unroll
+  for (int i = 0; i < CZS_ZT; ++i) {
+    const int kk = min(g * CZS_ZT + i, a.nz - 1);  // a chunk's tail repeats its last plane (not stored)
+    zk[i] = a.z[kk];
+    rph[i] = rs_phase(lam, zk[i]);
+    cf[i] = ws + ((size_t)kk * a.C + c) * a.tabStride + a.coef;
+  }
+  const float xlo = -(float)a.H * a.dx / 2.0f, xhi = (float)a.H * a.dx / 2.0f;
+  const float yw = lin(-(float)a.W * a.dy / 2.0f, (float)a.W * a.dy / 2.0f, a.W, w);
+  const float2* src = in + (size_t)bc * a.H * a.W + w;
+  const int h0 = hsi * a.hlen, h1 = min(a.H, h0 + a.hlen);
+  float2 acc[CZS_ZT];
+#pragma unroll
+  for (int i = 0; i < CZS_ZT; ++i) acc[i] = make_float2(0.f, 0.f);
+#pragma unroll 2
+  for (int h = h0; h < h1; ++h) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const f32x2 t = __builtin_nontemporal_load(reinterpret_cast<const f32x2*>(src + (size_t)h * a.W));
+    const float2 x = make_float2(t.x, t.y);
+    const float xh = lin(xlo, xhi, a.H, h);
+#pragma unroll
+    for (int i = 0; i < CZS_ZT; ++i) {
+      const float2 F = rs_kernel_fast(xh, yw, zk[i], k, rph[i]);
+      acc[i] = cadd(acc[i], cmul(cmul(x, F), cf[i][h]));
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < CZS_ZT; ++i) {
+    const int kk = g * CZS_ZT + i;
+    if (kk < a.nz) P[(((size_t)hsi * a.nz + kk) * a.BC + bc) * a.W + w] = acc[i];
+  }
+}
+
+// One pass-A Bluestein line per (k, b, c): S (its H splits summed in order) x preA -> np2 transform
+// pair -> out[k][bc][q] = cst F0(x_out[p], y_out[q]) postB[p] postA[q] y[q]
+template <int PN>
+__global__ void __launch_bounds__(1024) czt_slice_line(const float2* __restrict__ P, float2* __restrict__ out,
+                                                      const float2* __restrict__ ws, FftPlan pl, CztSliceArgs a) {
+  extern __shared__ float2 lds[];
+  const int kk = blockIdx.x / a.BC, bc = blockIdx.x - kk * a.BC;
+  const int c = bc % a.C;
+  const float lam = a.lam[c], z = a.z[kk];
+  const float k = 6.283185307179586f / lam;
+  const RsPhase rph = rs_phase(lam, z);
+  const float2* tab = ws + ((size_t)kk * a.C + c) * a.tabStride;
+  const float2* pre = tab + a.preA;
+  const float2* post = tab + a.postA;
+  const float2* ft = tab + a.ftA;
+  const float2* src = P + ((size_t)kk * a.BC + bc) * a.W;
+  const size_t sstride = (size_t)a.nz * a.BC * a.W;
+  float2* dst = out + ((size_t)kk * a.BC + bc) * a.outH;
+  const int m = a.W, M = a.outH;
+  const float xp = lin(-(float)a.outH * a.odx / 2.0f, (float)a.outH * a.odx / 2.0f, a.outH, a.row);
+  const float ylo = -(float)a.outW * a.ody / 2.0f, yhi = (float)a.outW * a.ody / 2.0f;
+  const float cst = ((z * a.odx) * a.ody) * lam;
+  const float2 pb = tab[a.postB];
+  auto load_x = [&](int w) {
+    if (w >= m) return make_float2(0.f, 0.f);
+    float2 s = src[w];
+    for (int i = 1; i < a.hs; ++i) s = cadd(s, src[i * sstride + w]);
+    return cmul(s, pre[w]);
+  };
+  auto store_y = [&](int j, float2 v) {
+    const int q = j - m;
+    if (q >= 0 && q < M) {
+      const float2 F0 = rs_kernel(xp, lin(ylo, yhi, a.outW, q), z, k, rph);
+      dst[q] = cscale(cmul(F0, cmul(cmul(v, post[q]), pb)), cst);
+    }
+  };
+  int tid = threadIdx.x;
+  if constexpr (PN > 0) {
+    using S = Pow2Sched<PN>;
+    constexpr int TT = CztGeo<PN>::T;
+    constexpr int RL = S::radix(S::NST - 1, false);
+    constexpr int MBL = PN / RL / TT;
+    float2 sp[MBL][RL];
+    const TwLds twl = load_tw_lds<PN>(tw_slot<PN>(lds), pl.tw, tid, blockDim.x);
+    auto ld0 = [&](int, int, int idx) { return load_x(idx); };
+    auto sv0 = [&](int mm, int r, int, float2 v) { sp[mm][r] = v; };
+    fft_pow2_run<false, PN, TT, false>(lds, twl, tid, ld0, sv0);
+    asm volatile("" : "+v"(tid));
+    auto ld1 = [&](int mm, int r, int idx) { return cmul(sp[mm][r], ft[idx]); };
+    auto sv1 = [&](int, int, int j, float2 v) { store_y(j, v); };
+    fft_pow2_run<true, PN, TT, true>(lds, twl, tid, ld1, sv1);
+  } else {
+    const int n = pl.n, nt = blockDim.x;
+    for (int j = tid; j < n; j += nt) lds[padx(j)] = load_x(j);
+    __syncthreads();
+    fft_lds<false>(lds, pl, tid, nt);
+    for (int j = tid; j < n; j += nt) lds[padx(j)] = cmul(lds[padx(j)], ft[j]);
+    __syncthreads();
+    fft_lds<true>(lds, pl, tid, nt);
+    for (int j = tid; j < n; j += nt) store_y(j, lds[padx(j)]);
+  }
+}
+
+static int czt_slice_validate(const thz_czt_slice_desc* d) {
+  if (!d) return fail(THZ_E_ARG, "null descriptor");
+  thz_czt_desc t{};
+  t.B = d->B, t.C = d->C, t.H = d->H, t.W = d->W, t.outH = d->outH, t.outW = d->outW;
+  t.wavelengths = d->wavelengths;
+  int e = czt_validate(&t);  // the planes' own shape rules
+  if (e) return e;
+  if (d->Z < 1 || d->Z > THZ_MAX_Z) return fail(THZ_E_ARG, "Z=%d outside [1, %d]", d->Z, THZ_MAX_Z);
+  if (!d->z) return fail(THZ_E_ARG, "null z");
+  if (d->row < 0 || d->row >= d->outW)
+    return fail(THZ_E_ARG, "row %d outside the valid range [0, %d) of the output rows", d->row, d->outW);
+  return THZ_OK;
+}
+
+// Workspace: [tables of min(Z, CZS_ZC) x C (plane, wavelength) blocks][P [hs][min(Z, CZS_ZC)][BC][W]]
+static void czt_slice_layout(const thz_czt_slice_desc* d, CztSliceArgs* a, size_t* tab_bytes, size_t* total) {
+  a->BC = d->B * d->C;
+  a->C = d->C;
+  a->H = d->H;
+  a->W = d->W;
+  a->outH = d->outH;
+  a->outW = d->outW;
+  a->row = d->row;
+  a->dx = d->dx;
+  a->dy = d->dy;
+  a->odx = d->odx;
+  a->ody = d->ody;
+  const double xo = (double)(float)((float)d->outH * d->odx / 2.0f);
+  const double yo = (double)(float)((float)d->outW * d->ody / 2.0f);
+  make_pass(&a->pa, d->W, d->outH, -xo, xo, false);
+  make_pass(&a->pb, d->H, d->outW, -yo, yo, false);
+  const int nzc = std::min(d->Z, CZS_ZC);
+  a->nz = nzc;
+  // split H until the collapse grid has about CZS_WAVES waves, at least 16 rows per split
+  const long waves = (long)((d->W + 63) / 64) * a->BC * ((nzc + CZS_ZT - 1) / CZS_ZT);
+  int hs = (int)std::min<long>(CZS_HS_MAX, (CZS_WAVES + waves - 1) / waves);
+  hs = std::max(1, std::min(hs, d->H / 16));
+  a->hlen = (d->H + hs - 1) / hs;
+  a->hs = (d->H + a->hlen - 1) / a->hlen;
+  size_t off = 0;
+  auto take = [&](size_t n) {
+    size_t o = off;
+    off += (n + 31) & ~(size_t)31;
+    return o;
+  };
+  a->preA = take(a->pa.m);
+  a->postA = take(a->pa.M);
+  a->ftA = take(a->pa.np2);
+  a->coef = take(a->pb.m);
+  a->postB = take(1);
+  a->tabStride = off;
+  for (int c = 0; c < d->C; ++c) a->lam[c] = d->wavelengths[c];
+  *tab_bytes = a256((size_t)nzc * d->C * a->tabStride * sizeof(float2));
+  *total = *tab_bytes + a256((size_t)a->hs * nzc * a->BC * d->W * sizeof(float2));
+}
+
+static int czt_slice_lds_attr() {
+  static std::once_flag once;
+  static hipError_t err = hipSuccess;
+  std::call_once(once, [] {
+    const int mx = (int)fft_lds_bytes(FFT_MAX_N);
+    const void* ks[] = {(const void*)czt_slice_line<0>,    (const void*)czt_slice_line<1024>,
+                        (const void*)czt_slice_line<2048>, (const void*)czt_slice_line<4096>,
+                        (const void*)czt_slice_line<8192>, (const void*)czt_slice_line<16384>};
+    for (const void* k : ks) {
+      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
+      if (e != hipSuccess) err = e;
+    }
+  });
+  if (err != hipSuccess) return fail(THZ_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(err));
+  return THZ_OK;
+}
+
 }  // namespace thz
 
 using namespace thz;
@@ -890,6 +1157,67 @@ extern "C" int thz_czt_forward(const thz_czt_desc* d, const void* in, void* out,
     }
     THZ_LAUNCH_CHECK();
     kt.stop();
+  }
+  return THZ_OK;
+}
+
+extern "C" int thz_czt_slice_workspace_size(const thz_czt_slice_desc* d, size_t* bytes) {
+  int e = czt_slice_validate(d);
+  if (e) return e;
+  if (!bytes) return fail(THZ_E_ARG, "null bytes");
+  CztSliceArgs a{};
+  size_t tab = 0;
+  czt_slice_layout(d, &a, &tab, bytes);
+  return THZ_OK;
+}
+
+extern "C" int thz_czt_slice_forward(const thz_czt_slice_desc* d, const void* in, void* out, void* workspace,
+                                     size_t workspace_bytes, thz_stream_t stream) {
+  int e = czt_slice_validate(d);
+  if (e) return e;
+  if (!in || !out) return fail(THZ_E_ARG, "null data pointer");
+  CztSliceArgs a{};
+  size_t tab = 0, need = 0;
+  czt_slice_layout(d, &a, &tab, &need);
+  if (!workspace || workspace_bytes < need)
+    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  const long wb = (d->W + CZS_THREADS - 1) / CZS_THREADS, ngmax = (a.nz + CZS_ZT - 1) / CZS_ZT;
+  if (wb * ngmax * a.hs * a.BC > 0x7fffffffL || (long)CZS_ZC * a.BC > 0x7fffffffL)
+    return fail(THZ_E_UNSUPPORTED, "CZT slice: B C = %d is too large for one launch", a.BC);
+  if ((e = czt_slice_lds_attr())) return e;
+  FftPlan plA;
+  if ((e = get_plan(a.pa.np2, &plA))) return e;
+  hipStream_t s = (hipStream_t)stream;
+  float2* ws = (float2*)workspace;
+  float2* P = (float2*)((char*)workspace + tab);
+  const int ntab = std::max({a.pa.m, a.pa.M, a.pa.np2, a.pb.m});
+  for (int k0 = 0; k0 < d->Z; k0 += CZS_ZC) {
+    a.nz = std::min(CZS_ZC, d->Z - k0);
+    for (int k = 0; k < a.nz; ++k) a.z[k] = d->z[k0 + k];
+    {
+      KernelTimer kt("czt_slice_tables", s);
+      hipLaunchKernelGGL(czt_slice_tables, dim3((ntab + 255) / 256, a.nz * d->C), dim3(256), 0, s, a, ws);
+      THZ_LAUNCH_CHECK();
+      // the filter spectra FFT_np2(1/h) of every (plane, wavelength) in place, one launch
+      if ((e = fft_rows_strided(ws + a.ftA, ws + a.ftA, a.nz * d->C, a.pa.np2, a.tabStride, 0, s))) return e;
+      kt.stop();
+    }
+    {
+      KernelTimer kt("czt_slice_collapse", s);
+      const int ng = (a.nz + CZS_ZT - 1) / CZS_ZT;
+      hipLaunchKernelGGL(czt_slice_collapse, dim3((unsigned)(wb * ng * a.hs * a.BC)), dim3(CZS_THREADS), 0, s,
+                         (const float2*)in, P, (const float2*)ws, a);
+      THZ_LAUNCH_CHECK();
+      kt.stop();
+    }
+    {
+      KernelTimer kt("czt_slice_line", s);
+      THZ_CZT_SWITCH(a.pa.np2, czt_slice_line, dim3(a.nz * a.BC), dim3(threads_pow2_or(a.pa.np2)),
+                     fft_lds_bytes_io(a.pa.np2), s, (const float2*)P, (float2*)out + (size_t)k0 * a.BC * d->outH,
+                     (const float2*)ws, plA, a);
+      THZ_LAUNCH_CHECK();
+      kt.stop();
+    }
   }
   return THZ_OK;
 }

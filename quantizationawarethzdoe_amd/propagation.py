@@ -570,6 +570,38 @@ def czt_apply(data, wavelengths, spacing, z, outH, outW, odx, ody, adjoint=False
     return out
 
 
+def _czt_slice_desc(B, C, H, W, outH, outW, spacing, odx, ody, wavelengths, zs, row):
+    """thz_czt_slice_desc (the host arrays are kept alive by the descriptor)."""
+    wl = _lib.float_array(wavelengths)
+    zv = _lib.float_array(zs)
+    d = _lib.CztSliceDesc(B=int(B), C=int(C), H=int(H), W=int(W), outH=int(outH), outW=int(outW),
+                          dx=float(spacing[0]), dy=float(spacing[1]), odx=float(odx), ody=float(ody), Z=len(zs),
+                          z=ctypes.cast(zv, ctypes.POINTER(ctypes.c_float)),
+                          wavelengths=ctypes.cast(wl, ctypes.POINTER(ctypes.c_float)), row=int(row))
+    d._keep = (wl, zv)
+    return d
+
+
+def czt_slice_apply(data, wavelengths, spacing, zs, row, outH, outW, odx, ody, out=None):
+    """Raw launch of the CZT z-x slice (thz_czt_slice_forward): data [B,C,H,W] complex64 -> [Z,B,C,outH],
+    output row ``row`` (the p of out[b, c, p, q]) of every plane of ``zs`` (at most THZ_MAX_Z), equal to
+    czt_apply(..., z, ...)[:, :, row, :] per z without forming the planes.  Forward only."""
+    _require_device(data, "CZT slice")
+    if data.dtype != torch.complex64:
+        raise TypeError(f"CZT slice kernels compute in complex64; got {data.dtype}")
+    L = _lib.lib()
+    data = data.contiguous()
+    B, C, H, W = data.shape
+    d = _czt_slice_desc(B, C, H, W, outH, outW, spacing, odx, ody, wavelengths, zs, row)
+    shape = (len(zs), B, C, int(outH))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex64, device=data.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.complex64 or not out.is_contiguous():
+        raise ValueError(f"CZT slice: out must be a contiguous complex64 {shape} tensor")
+    _launch(L.thz_czt_slice_workspace_size, L.thz_czt_slice_forward, d, data.device, data, out)
+    return out
+
+
 def rsc_apply(data, wavelengths, spacing, z, vectorial=False, adjoint=False, field_hw=None):
     """Rayleigh-Sommerfeld convolution (Props/RSC_Prop.py:170-321) on the HIP kernels.
 
