@@ -56,7 +56,8 @@ typedef void* thz_stream_t; /* hipStream_t */
  * thz_adam_step, 9 thz_asm_slice_workspace_size and thz_asm_slice_forward;
  * thz_asm_slice_adjoint_workspace_size and thz_asm_slice_adjoint (library 0.6.0) changed no struct and
  * are purely additive, so the version stays 9 -- a caller detects them by symbol; likewise
- * thz_czt_slice_workspace_size and thz_czt_slice_forward with their own new thz_czt_slice_desc):
+ * thz_czt_slice_workspace_size and thz_czt_slice_forward with their own new thz_czt_slice_desc, and
+ * thz_czt_slice_adjoint_workspace_size and thz_czt_slice_adjoint on the same descriptor):
  * a caller compares thz_abi_version()
  * with the THZ_ABI_VERSION it was compiled against before its first call, since a shorter
  * struct from an older header would make the library read past it.  Descriptors are plain C
@@ -206,7 +207,8 @@ int thz_czt_forward(const thz_czt_desc* d, const void* in, void* out, void* work
  * preB[h] gB[p + H - h] for four planes per read of the field, then one W-axis Bluestein line of
  * np2 = 2^ceil(log2(W + outH - 1)) points per (k, b, c).  No intermediate of a plane's size, no
  * second pass, no per-z table cache; two calls with the same inputs are bit-identical (H is split in
- * a fixed way and its partial sums are added in order, no atomics).  Forward only, host z[] only.
+ * a fixed way and its partial sums are added in order, no atomics).  Forward only (its adjoint is
+ * thz_czt_slice_adjoint below), host z[] only.
  * Validation, all before any device call: the shape rules of thz_czt_forward (square output,
  * C <= THZ_MAX_WAVELENGTHS, THZ_E_ARG for a power-of-two Bluestein length, THZ_E_UNSUPPORTED past the
  * longest transform); a bad row, Z outside 1 .. THZ_MAX_Z or a null pointer THZ_E_ARG; a short or
@@ -230,6 +232,28 @@ typedef struct thz_czt_slice_desc {
 int thz_czt_slice_workspace_size(const thz_czt_slice_desc* d, size_t* bytes);
 int thz_czt_slice_forward(const thz_czt_slice_desc* d, const void* in /* [B,C,H,W] */,
                           void* out /* [Z,B,C,outH] */, void* workspace, size_t workspace_bytes,
+                          thz_stream_t stream);
+/*
+ * Adjoint of the CZT z-x slice (the autograd backward of thz_czt_slice_forward), same descriptor:
+ *   grad_out [Z, B, C, outH] -> grad_in [B, C, H, W] = sum over k of A_{z_k,row}^H grad_out[k]
+ * Per chunk of 16 planes, with the forward's tables: one W-axis Bluestein line per (k, b, c) in the
+ * adjoint form (conjugated chirps, filter spectrum and F0; windows exchanged) gives
+ * T_k[b,c,w], then an expand kernel adds sum_k conj(F_{z_k,c}(x_h, y_w) coef_kc[h]) T_k[b,c,w] to
+ * grad_in[b,c,h,w] -- one RS-kernel evaluation per (element, plane), as the forward's collapse.  The
+ * first chunk stores grad_in (it may be uninitialised memory; every element is written), later chunks
+ * read, add and store it on the same stream: no memset, no atomics, a fixed summation order, so two
+ * calls with the same inputs are bit-identical.  Purely additive: THZ_ABI_VERSION stays 9, a caller
+ * detects the entries by symbol.  Validation as the forward's, all before any device call: a bad
+ * row, Z outside 1 .. THZ_MAX_Z or a null pointer THZ_E_ARG; a short or null workspace
+ * THZ_E_WORKSPACE (the message names the size).
+ * Workspace, with zc = min(Z, 16) and r32 as above:
+ *   8 zc C (r32(W) + r32(outH) + np2 + r32(H) + 32)     tables per (plane, wavelength)
+ * + 8 zc B C W                                           T
+ * bytes, each part rounded up to 256 -- nothing of a plane's size, no growth with Z past one chunk.
+ */
+int thz_czt_slice_adjoint_workspace_size(const thz_czt_slice_desc* d, size_t* bytes);
+int thz_czt_slice_adjoint(const thz_czt_slice_desc* d, const void* grad_out /* [Z,B,C,outH] */,
+                          void* grad_in /* [B,C,H,W] */, void* workspace, size_t workspace_bytes,
                           thz_stream_t stream);
 
 /*
@@ -572,7 +596,7 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * duration and launch count for one kernel name ("asm_rows_fwd", "asm_cols", "asm_rows_inv"; the
  * z-x slice: "asm_rows_fwd", "asm_cols_slice", "asm_rows_slice"; its adjoint: "asm_rows_fwd",
  * "asm_cols_slice_adj", "asm_rows_inv"; the CZT z-x slice: "czt_slice_tables", "czt_slice_collapse",
- * "czt_slice_line"; ...).
+ * "czt_slice_line"; its adjoint: "czt_slice_tables", "czt_slice_line_adj", "czt_slice_expand"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

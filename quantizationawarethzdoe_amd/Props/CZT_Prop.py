@@ -143,7 +143,7 @@ class CZT_prop(nn.Module):
         return torch.stack([self._plane(x, field, zh, outH, outW, odx, ody) for zh in _z_host(z_list)])
 
     def propagate_zx(self, field: ElectricField, z_list, row=None, axis="x", outputHeight=None, outputWidth=None,
-                     outputPixel_dx=None, outputPixel_dy=None) -> torch.Tensor:
+                     outputPixel_dx=None, outputPixel_dy=None, grad="planes") -> torch.Tensor:
         """Additive API: one zoomed output row of every plane of ``z_list`` -> [Z, B, C, outH], equal to
         ``propagate_planes(field, z_list, ...)[..., row, :]`` -- the x-z cross-section of a focal region
         on the zoomed grid (Props/CZT_Prop.py:260-262: "useful for imaging light in the focal plane:
@@ -162,9 +162,19 @@ class CZT_prop(nn.Module):
         slice entry refuses as unsupported -- propagates the full planes in z-chunks whose temporary
         stays under 10 GiB and slices each chunk, differentiably.  Geometries ``forward`` refuses
         (a non-square output, a power-of-two Bluestein length) raise as it does; the one empty
-        [B, C, 1, 0] geometry of ``forward`` gives the correspondingly empty slice."""
+        [B, C, 1, 0] geometry of ``forward`` gives the correspondingly empty slice.
+
+        ``grad`` chooses what serves a differentiated call, as on ASM_prop.propagate_zx.  ``"planes"``
+        (the default) is the behaviour above.  ``"slice"``: the slice kernels serve a complex64 device
+        field whether or not it requires grad, and the backward is their own adjoint
+        (thz_czt_slice_adjoint: one adjoint Bluestein line per (z, b, c) and an expand kernel that
+        mirrors the collapse, nothing of a plane's size per z in either direction); ``axis="y"``
+        transposes outside the slice (torch differentiates the transpose).  The other inputs listed
+        above still take the full planes.  Any other value is a ValueError."""
         if axis not in ("x", "y"):
             raise ValueError(f"propagate_zx: axis must be 'x' or 'y', got {axis!r}")
+        if grad not in ("planes", "slice"):
+            raise ValueError(f"propagate_zx: grad must be 'planes' or 'slice', got {grad!r}")
         outH, outW, odx, ody = self._out_grid(field, outputHeight, outputWidth, outputPixel_dx, outputPixel_dy)
         n = outW if axis == "x" else outH
         if row is None:
@@ -178,16 +188,20 @@ class CZT_prop(nn.Module):
         x = _prop.kernel_dtype(field.data, "CZT_prop", field.wavelengths)
         B, C, H, W = x.shape
         max_z = _prop._lib.THZ_MAX_Z
-        native = (x.dtype == torch.complex64 and x.is_cuda and not (torch.is_grad_enabled() and x.requires_grad)
+        diff = torch.is_grad_enabled() and x.requires_grad
+        native = (x.dtype == torch.complex64 and x.is_cuda and not (diff and grad == "planes")
                   and not self._empty_plane(H, W, outH, outW) and (axis == "x" or sp[0] == sp[1]))
         if native:
             wl = tuple(field.wavelengths_host)
             if axis == "y":
-                xs, geo = x.detach().transpose(-1, -2).contiguous(), ((sp[1], sp[0]), outW, outH, ody, odx)
+                xs, geo = x.transpose(-1, -2), ((sp[1], sp[0]), outW, outH, ody, odx)
             else:
-                xs, geo = x.detach(), (sp, outH, outW, odx, ody)
-            out = torch.empty((len(zs), B, C, geo[1]), dtype=torch.complex64, device=x.device)
+                xs, geo = x, (sp, outH, outW, odx, ody)
             try:
+                if diff:  # grad="slice": the slice kernels forward, thz_czt_slice_adjoint backward
+                    return _prop.czt_propagate_zx(xs, wl, geo[0], zs, row, geo[1], geo[2], geo[3], geo[4])
+                xs = xs.detach().contiguous()
+                out = torch.empty((len(zs), B, C, geo[1]), dtype=torch.complex64, device=x.device)
                 for k in range(0, len(zs), max_z):
                     _prop.czt_slice_apply(xs, wl, geo[0], zs[k:k + max_z], row, geo[1], geo[2], geo[3], geo[4],
                                           out=out[k:k + max_z])

@@ -33,6 +33,7 @@ EXPORTED = [
     "thz_asm_slice_adjoint_workspace_size", "thz_asm_slice_adjoint",
     "thz_czt_workspace_size", "thz_czt_forward",
     "thz_czt_slice_workspace_size", "thz_czt_slice_forward",
+    "thz_czt_slice_adjoint_workspace_size", "thz_czt_slice_adjoint",
     "thz_rsc_workspace_size", "thz_rsc_forward",
     "thz_doe_modulate_forward", "thz_doe_modulate_backward", "thz_quant_forward", "thz_quant_backward",
     "thz_doe_quant_backward", "thz_radial_quant_backward",
@@ -245,6 +246,9 @@ def _declare(lib):
     lib.thz_czt_forward.argtypes = [ctypes.POINTER(CztDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.thz_czt_slice_workspace_size.argtypes = [ctypes.POINTER(CztSliceDesc), ctypes.POINTER(c_size_t)]
     lib.thz_czt_slice_forward.argtypes = [ctypes.POINTER(CztSliceDesc), c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]
+    lib.thz_czt_slice_adjoint_workspace_size.argtypes = [ctypes.POINTER(CztSliceDesc), ctypes.POINTER(c_size_t)]
+    lib.thz_czt_slice_adjoint.argtypes = [ctypes.POINTER(CztSliceDesc), c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p]
     lib.thz_gaussian_beam.argtypes = [ctypes.POINTER(GaussDesc), c_void_p, c_void_p]
     lib.thz_thin_lens.argtypes = [ctypes.POINTER(LensDesc), c_void_p, c_void_p, c_void_p]

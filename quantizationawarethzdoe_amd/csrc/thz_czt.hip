@@ -1015,6 +1015,119 @@ __global__ void __launch_bounds__(1024) czt_slice_line(const float2* __restrict_
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Adjoint of the z-x slice (autograd backward): gin = sum_k collapse_k^H line_k^H g_k, per chunk of
+// CZS_ZC planes with the forward's tables.
+//   line adjoint (the form above czt_cols_adj), one workgroup per (k, b, c):
+//     Z[(q + m) mod N] = conj(postA[q]) conj(cst F0(x_p, y_q) postB[p]) g[k,bc,q]  (q < outH, else 0)
+//     T_k[bc,w]        = conj(preA[w]) IFFT_N(FFT_N(Z) conj(ft))[w]                (w < W)
+//   expand (the collapse kernel mirrored):
+//     gin[bc,h,w] (+)= sum_{k in chunk} conj(F_{z_k,c}(x_h, y_w)) conj(coef_kc[h]) T_k[bc,w]
+// ---------------------------------------------------------------------------------------------
+#ifndef CZS_XT
+#define CZS_XT CZS_ZT   // planes whose T values a thread of the expand kernel holds at a time
+#endif
+constexpr int CZS_XR = 8;  // rows of gin per workgroup of the expand kernel (accumulators in registers)
+
+template <int PN>
+__global__ void __launch_bounds__(1024) czt_slice_line_adj(const float2* __restrict__ G, float2* __restrict__ T,
+                                                          const float2* __restrict__ ws, FftPlan pl, CztSliceArgs a) {
+  extern __shared__ float2 lds[];
+  const int kk = blockIdx.x / a.BC, bc = blockIdx.x - kk * a.BC;
+  const int c = bc % a.C;
+  const float lam = a.lam[c], z = a.z[kk];
+  const float k = 6.283185307179586f / lam;
+  const RsPhase rph = rs_phase(lam, z);
+  const float2* tab = ws + ((size_t)kk * a.C + c) * a.tabStride;
+  const float2* pre = tab + a.preA;
+  const float2* post = tab + a.postA;
+  const float2* ft = tab + a.ftA;
+  const float2* src = G + ((size_t)kk * a.BC + bc) * a.outH;
+  float2* dst = T + ((size_t)kk * a.BC + bc) * a.W;
+  const int m = a.W, M = a.outH, N = pl.n;
+  const float xp = lin(-(float)a.outH * a.odx / 2.0f, (float)a.outH * a.odx / 2.0f, a.outH, a.row);
+  const float ylo = -(float)a.outW * a.ody / 2.0f, yhi = (float)a.outW * a.ody / 2.0f;
+  const float cst = ((z * a.odx) * a.ody) * lam;
+  const float2 pb = conjf2(tab[a.postB]);
+  auto load_x = [&](int j) {
+    int q = j - m;
+    if (q < 0) q += N;
+    if (q >= M) return make_float2(0.f, 0.f);
+    const float2 F0 = rs_kernel(xp, lin(ylo, yhi, a.outW, q), z, k, rph);
+    return cmul(cmul(conjf2(post[q]), pb), cscale(cmul(conjf2(F0), src[q]), cst));
+  };
+  auto store_y = [&](int j, float2 v) {
+    if (j < m) dst[j] = cmul(conjf2(pre[j]), v);
+  };
+  czt_adj_line<PN>(lds, pl, ft, load_x, store_y);
+}
+
+// Lanes along w (coalesced stores of gin rows), CZS_XR rows per workgroup with their sums in
+// registers; the planes of the chunk go CZS_XT at a time: their T values, distances and phases sit
+// in registers while the thread walks its rows, the conj(coef) values are wave-uniform loads.  One RS
+// kernel evaluation per (element, plane), as in the collapse kernel.  FIRST: the call's first chunk
+// stores gin without reading it (the caller passes uninitialised memory); later chunks add to it.
+// The order of the sum is fixed: planes ascending within a chunk, chunks ascending.
+template <bool FIRST>
+__global__ void __launch_bounds__(CZS_THREADS) czt_slice_expand(const float2* __restrict__ T, float2* __restrict__ gin,
+                                                                const float2* __restrict__ ws, CztSliceArgs a) {
+  __shared__ float kzm[CZS_ZC];
+  const int wb = (a.W + CZS_THREADS - 1) / CZS_THREADS, nhb = (a.H + CZS_XR - 1) / CZS_XR;
+  int id = blockIdx.x;
+  const int bw = id % wb;
+  id /= wb;
+  const int hb = id % nhb, bc = id / nhb;
+  const int c = bc % a.C;
+  const float lam = a.lam[c];
+  const float k = 6.283185307179586f / lam;
+  // (k |z|) mod 2 pi of every plane of the chunk, once per workgroup (double arithmetic)
+  if ((int)threadIdx.x < a.nz) kzm[threadIdx.x] = rs_phase(lam, a.z[threadIdx.x]).kzmod;
+  __syncthreads();
+  const int w = bw * CZS_THREADS + (int)threadIdx.x;
+  if (w >= a.W) return;
+  const float xlo = -(float)a.H * a.dx / 2.0f, xhi = (float)a.H * a.dx / 2.0f;
+  const float yw = lin(-(float)a.W * a.dy / 2.0f, (float)a.W * a.dy / 2.0f, a.W, w);
+  const int h0 = hb * CZS_XR;
+  float2* dst = gin + ((size_t)bc * a.H + h0) * a.W + w;
+  float2 acc[CZS_XR];
+#pragma unroll
+  for (int r = 0; r < CZS_XR; ++r) acc[r] = make_float2(0.f, 0.f);
+  for (int g0 = 0; g0 < a.nz; g0 += CZS_XT) {
+    float zk[CZS_XT];
+    RsPhase rph[CZS_XT];
+    const float2* cf[CZS_XT];
+    float2 t[CZS_XT];
+#pragma unroll
+    for (int i = 0; i < CZS_XT; ++i) {
+      const int kk = min(g0 + i, a.nz - 1);  // a chunk's tail repeats its last plane with T = 0
+      zk[i] = a.z[kk];
+      rph[i].kzmod = kzm[kk];
+      rph[i].k = k;
+      cf[i] = ws + ((size_t)kk * a.C + c) * a.tabStride + a.coef;
+      t[i] = g0 + i < a.nz ? T[((size_t)kk * a.BC + bc) * a.W + w] : make_float2(0.f, 0.f);
+    }
+#pragma unroll
+    for (int r = 0; r < CZS_XR; ++r) {
+      const int h = h0 + r;
+      if (h < a.H) {
+        const float xh = lin(xlo, xhi, a.H, h);
+#pragma unroll
+        for (int i = 0; i < CZS_XT; ++i) {
+          const float2 F = rs_kernel_fast(xh, yw, zk[i], k, rph[i]);
+          acc[r] = cadd(acc[r], cmul(conjf2(cmul(F, cf[i][h])), t[i]));
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < CZS_XR; ++r) {
+    if (h0 + r < a.H) {
+      float2* p = dst + (size_t)r * a.W;
+      *p = FIRST ? acc[r] : cadd(*p, acc[r]);
+    }
+  }
+}
+
 static int czt_slice_validate(const thz_czt_slice_desc* d) {
   if (!d) return fail(THZ_E_ARG, "null descriptor");
   thz_czt_desc t{};
@@ -1071,6 +1184,14 @@ static void czt_slice_layout(const thz_czt_slice_desc* d, CztSliceArgs* a, size_
   *total = *tab_bytes + a256((size_t)a->hs * nzc * a->BC * d->W * sizeof(float2));
 }
 
+// The adjoint's workspace: [the same tables][T [min(Z, CZS_ZC)][BC][W]] (H is not reduced: no splits)
+static void czt_slice_adj_layout(const thz_czt_slice_desc* d, CztSliceArgs* a, size_t* tab_bytes, size_t* total) {
+  czt_slice_layout(d, a, tab_bytes, total);
+  a->hs = 1;
+  a->hlen = d->H;
+  *total = *tab_bytes + a256((size_t)a->nz * a->BC * d->W * sizeof(float2));
+}
+
 static int czt_slice_lds_attr() {
   static std::once_flag once;
   static hipError_t err = hipSuccess;
@@ -1078,7 +1199,10 @@ static int czt_slice_lds_attr() {
     const int mx = (int)fft_lds_bytes(FFT_MAX_N);
     const void* ks[] = {(const void*)czt_slice_line<0>,    (const void*)czt_slice_line<1024>,
                         (const void*)czt_slice_line<2048>, (const void*)czt_slice_line<4096>,
-                        (const void*)czt_slice_line<8192>, (const void*)czt_slice_line<16384>};
+                        (const void*)czt_slice_line<8192>, (const void*)czt_slice_line<16384>,
+                        (const void*)czt_slice_line_adj<0>,    (const void*)czt_slice_line_adj<1024>,
+                        (const void*)czt_slice_line_adj<2048>, (const void*)czt_slice_line_adj<4096>,
+                        (const void*)czt_slice_line_adj<8192>, (const void*)czt_slice_line_adj<16384>};
     for (const void* k : ks) {
       hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
       if (e != hipSuccess) err = e;
@@ -1215,6 +1339,66 @@ extern "C" int thz_czt_slice_forward(const thz_czt_slice_desc* d, const void* in
       THZ_CZT_SWITCH(a.pa.np2, czt_slice_line, dim3(a.nz * a.BC), dim3(threads_pow2_or(a.pa.np2)),
                      fft_lds_bytes_io(a.pa.np2), s, (const float2*)P, (float2*)out + (size_t)k0 * a.BC * d->outH,
                      (const float2*)ws, plA, a);
+      THZ_LAUNCH_CHECK();
+      kt.stop();
+    }
+  }
+  return THZ_OK;
+}
+
+extern "C" int thz_czt_slice_adjoint_workspace_size(const thz_czt_slice_desc* d, size_t* bytes) {
+  int e = czt_slice_validate(d);
+  if (e) return e;
+  if (!bytes) return fail(THZ_E_ARG, "null bytes");
+  CztSliceArgs a{};
+  size_t tab = 0;
+  czt_slice_adj_layout(d, &a, &tab, bytes);
+  return THZ_OK;
+}
+
+extern "C" int thz_czt_slice_adjoint(const thz_czt_slice_desc* d, const void* grad_out, void* grad_in,
+                                     void* workspace, size_t workspace_bytes, thz_stream_t stream) {
+  int e = czt_slice_validate(d);
+  if (e) return e;
+  if (!grad_out || !grad_in) return fail(THZ_E_ARG, "null data pointer");
+  CztSliceArgs a{};
+  size_t tab = 0, need = 0;
+  czt_slice_adj_layout(d, &a, &tab, &need);
+  if (!workspace || workspace_bytes < need)
+    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  const long wb = (d->W + CZS_THREADS - 1) / CZS_THREADS, nhb = (d->H + CZS_XR - 1) / CZS_XR;
+  if (wb * nhb * a.BC > 0x7fffffffL || (long)CZS_ZC * a.BC > 0x7fffffffL)
+    return fail(THZ_E_UNSUPPORTED, "CZT slice adjoint: B C = %d is too large for one launch", a.BC);
+  if ((e = czt_slice_lds_attr())) return e;
+  FftPlan plA;
+  if ((e = get_plan(a.pa.np2, &plA))) return e;
+  hipStream_t s = (hipStream_t)stream;
+  float2* ws = (float2*)workspace;
+  float2* T = (float2*)((char*)workspace + tab);
+  const int ntab = std::max({a.pa.m, a.pa.M, a.pa.np2, a.pb.m});
+  for (int k0 = 0; k0 < d->Z; k0 += CZS_ZC) {
+    a.nz = std::min(CZS_ZC, d->Z - k0);
+    for (int k = 0; k < a.nz; ++k) a.z[k] = d->z[k0 + k];
+    {
+      KernelTimer kt("czt_slice_tables", s);
+      hipLaunchKernelGGL(czt_slice_tables, dim3((ntab + 255) / 256, a.nz * d->C), dim3(256), 0, s, a, ws);
+      THZ_LAUNCH_CHECK();
+      if ((e = fft_rows_strided(ws + a.ftA, ws + a.ftA, a.nz * d->C, a.pa.np2, a.tabStride, 0, s))) return e;
+      kt.stop();
+    }
+    {
+      KernelTimer kt("czt_slice_line_adj", s);
+      THZ_CZT_SWITCH(a.pa.np2, czt_slice_line_adj, dim3(a.nz * a.BC), dim3(threads_pow2_or(a.pa.np2)),
+                     fft_lds_bytes_io(a.pa.np2), s, (const float2*)grad_out + (size_t)k0 * a.BC * d->outH, T,
+                     (const float2*)ws, plA, a);
+      THZ_LAUNCH_CHECK();
+      kt.stop();
+    }
+    {
+      // the first chunk stores grad_in, every later one reads, adds and stores it (same stream)
+      KernelTimer kt("czt_slice_expand", s);
+      hipLaunchKernelGGL(k0 == 0 ? czt_slice_expand<true> : czt_slice_expand<false>, dim3((unsigned)(wb * nhb * a.BC)),
+                         dim3(CZS_THREADS), 0, s, (const float2*)T, (float2*)grad_in, (const float2*)ws, a);
       THZ_LAUNCH_CHECK();
       kt.stop();
     }

@@ -585,7 +585,8 @@ def _czt_slice_desc(B, C, H, W, outH, outW, spacing, odx, ody, wavelengths, zs, 
 def czt_slice_apply(data, wavelengths, spacing, zs, row, outH, outW, odx, ody, out=None):
     """Raw launch of the CZT z-x slice (thz_czt_slice_forward): data [B,C,H,W] complex64 -> [Z,B,C,outH],
     output row ``row`` (the p of out[b, c, p, q]) of every plane of ``zs`` (at most THZ_MAX_Z), equal to
-    czt_apply(..., z, ...)[:, :, row, :] per z without forming the planes.  Forward only."""
+    czt_apply(..., z, ...)[:, :, row, :] per z without forming the planes.  Forward only;
+    czt_propagate_zx is the differentiable form (backward: czt_slice_adjoint)."""
     _require_device(data, "CZT slice")
     if data.dtype != torch.complex64:
         raise TypeError(f"CZT slice kernels compute in complex64; got {data.dtype}")
@@ -600,6 +601,56 @@ def czt_slice_apply(data, wavelengths, spacing, zs, row, outH, outW, odx, ody, o
         raise ValueError(f"CZT slice: out must be a contiguous complex64 {shape} tensor")
     _launch(L.thz_czt_slice_workspace_size, L.thz_czt_slice_forward, d, data.device, data, out)
     return out
+
+
+def czt_slice_adjoint(g, wavelengths, spacing, zs, row, outH, outW, odx, ody, field_hw, out=None):
+    """Raw launch of the CZT z-x slice's adjoint (thz_czt_slice_adjoint): the cotangent g [Z,B,C,outH]
+    complex64 of czt_slice_apply(x [B,C,H,W], ...) with (H, W) = field_hw -> [B,C,H,W], the sum over
+    the planes of each plane's adjoint -- czt_apply(g placed at row ``row`` of a zero plane,
+    adjoint=True) per z, summed, without forming a plane.  At most THZ_MAX_Z planes.  ``out``, when
+    given, is a contiguous complex64 [B,C,H,W] tensor; every element of it is overwritten."""
+    _require_device(g, "CZT slice adjoint")
+    if g.dtype != torch.complex64:
+        raise TypeError(f"CZT slice kernels compute in complex64; got {g.dtype}")
+    L = _lib.lib()
+    g = g.contiguous()
+    Z, B, C, n = g.shape
+    if Z != len(zs) or n != int(outH):
+        raise ValueError(f"CZT slice adjoint: gradient {tuple(g.shape)} is not [{len(zs)}, B, C, {int(outH)}]")
+    H, W = (int(v) for v in field_hw)
+    d = _czt_slice_desc(B, C, H, W, outH, outW, spacing, odx, ody, wavelengths, zs, row)
+    shape = (B, C, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex64, device=g.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.complex64 or not out.is_contiguous():
+        raise ValueError(f"CZT slice adjoint: out must be a contiguous complex64 {shape} tensor")
+    _launch(L.thz_czt_slice_adjoint_workspace_size, L.thz_czt_slice_adjoint, d, g.device, g, out)
+    return out
+
+
+class _CztSliceFunction(torch.autograd.Function):
+    """The CZT z-x slice with its native backward: forward czt_slice_apply, backward
+    czt_slice_adjoint.  A linear map: nothing is saved but the configuration."""
+
+    @staticmethod
+    def forward(ctx, data, wavelengths, spacing, zs, row, outH, outW, odx, ody):
+        ctx.cfg = (wavelengths, spacing, zs, row, outH, outW, odx, ody, tuple(data.shape[-2:]))
+        return czt_slice_apply(data, wavelengths, spacing, zs, row, outH, outW, odx, ody)
+
+    @staticmethod
+    def backward(ctx, g):
+        wavelengths, spacing, zs, row, outH, outW, odx, ody, hw = ctx.cfg
+        gin = czt_slice_adjoint(g, wavelengths, spacing, zs, row, outH, outW, odx, ody, hw)
+        return gin, None, None, None, None, None, None, None, None
+
+
+def czt_propagate_zx(data, wavelengths, spacing, zs, row, outH, outW, odx, ody):
+    """Differentiable CZT z-x slice on the slice kernels, forward and backward: [B,C,H,W] complex64 ->
+    [Z,B,C,outH], output row ``row`` of every plane of ``zs`` (any length: chunks of THZ_MAX_Z planes)."""
+    wl, sp, zs = list(map(float, wavelengths)), tuple(map(float, spacing)), list(map(float, zs))
+    outs = [_CztSliceFunction.apply(data, wl, sp, zs[k:k + _lib.THZ_MAX_Z], int(row), int(outH), int(outW),
+                                    float(odx), float(ody)) for k in range(0, len(zs), _lib.THZ_MAX_Z)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
 def rsc_apply(data, wavelengths, spacing, z, vectorial=False, adjoint=False, field_hw=None):
