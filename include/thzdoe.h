@@ -57,7 +57,8 @@ typedef void* thz_stream_t; /* hipStream_t */
  * thz_asm_slice_adjoint_workspace_size and thz_asm_slice_adjoint (library 0.6.0) changed no struct and
  * are purely additive, so the version stays 9 -- a caller detects them by symbol; likewise
  * thz_czt_slice_workspace_size and thz_czt_slice_forward with their own new thz_czt_slice_desc, and
- * thz_czt_slice_adjoint_workspace_size and thz_czt_slice_adjoint on the same descriptor):
+ * thz_czt_slice_adjoint_workspace_size and thz_czt_slice_adjoint on the same descriptor, and
+ * thz_rsc_slice_workspace_size and thz_rsc_slice_forward with their new thz_rsc_slice_desc):
  * a caller compares thz_abi_version()
  * with the THZ_ABI_VERSION it was compiled against before its first call, since a shorter
  * struct from an older header would make the library read past it.  Descriptors are plain C
@@ -279,6 +280,50 @@ typedef struct thz_rsc_desc {
 int thz_rsc_workspace_size(const thz_rsc_desc* d, size_t* bytes);
 int thz_rsc_forward(const thz_rsc_desc* d, const void* in, void* out, void* workspace, size_t workspace_bytes,
                     thz_stream_t stream);
+
+/*
+ * RSC / VRS z-x slice: one output row of every plane of a z-sweep, without forming the planes -- the
+ * x-z cross-section of a focal region on the Rayleigh-Sommerfeld convolution (Props/RSC_Prop.py:170-215,
+ * vectorial :265-321, called once per plane keeping out[..., row, :]).  Purely additive (no struct
+ * changed): THZ_ABI_VERSION stays 9, a caller detects the entries by symbol.
+ *   in [B, C, H, W] -> out [Z, Bo, C, Pw - W] == thz_rsc_forward(z = z[k])'s out[:, :, row, :] for every k
+ * row indexes the output window, 0 <= row < Ph - H.  With x = linspace(-Ph dx/2, Ph dx/2, Ph),
+ * y = linspace(-Pw dx/2, Pw dx/2, Pw) (dx on both axes, :83-84) the 2-D circular convolution at output
+ * row H + row is a sum of H one-dimensional ones, and it never wraps (1 <= H + row - i <= Ph - 1):
+ *   out[k,b,c,q] = dx dy IFFT_Pw( sum_{i<H} FFT_Pw(in[b,c,i,:] zero-padded)[m]
+ *                                           FFT_Pw(RS_{z_k,c}(x[H + row - i], y[:]))[m] )[W + q]
+ * The input rows' spectra Uh are formed once per call (they do not depend on z; VRS's Ez does,
+ * through r = sqrt(x^2 + y^2 + z^2) of :294-303, so its rows are formed per plane of the chunk); a
+ * kernel row's spectrum serves every b.  Per chunk of zc = min(Z, 32) planes one accumulate launch
+ * (kernel row -> Pw-point transform in LDS -> x Uh -> partial sums over hs fixed splits of the input
+ * rows, in registers) and one line launch (the hs partials added in index order, one inverse Pw-point
+ * transform per (k, b, c), x dx dy / Pw, elements [W, Pw)).  No transform along H, no Ph x Pw kernel
+ * table or its 2-D FFT; two calls with the same inputs are bit-identical (fixed split, fixed order,
+ * no atomics).  Forward only, host z[] only.
+ * Validation, all before any device call: the shape rules of thz_rsc_forward (THZ_E_ARG for a bad
+ * shape, vectorial with B < 2 or null wavelengths; THZ_E_UNSUPPORTED for C > THZ_MAX_WAVELENGTHS or a
+ * grid past the longest transform); a bad row, Z outside 1 .. THZ_MAX_Z or a null pointer THZ_E_ARG; a
+ * short or null workspace THZ_E_WORKSPACE (the message names the size).
+ * Workspace, with hs = max(1, min(H, 64, floor(2048 / (32 C)))) (a function of H and C alone, so a
+ * plane is summed alike whatever batch it is part of):
+ *   8 (vectorial ? 2 + zc : B) C H Pw      Uh, the input rows' spectra
+ * + 8 zc Bo C hs Pw                        P, one chunk's partial sums
+ * bytes, each part rounded up to 256 -- no Ph x Pw table, no growth with Z past one chunk.
+ */
+typedef struct thz_rsc_slice_desc {
+  int B, C, H, W;
+  int vectorial;            /* as thz_rsc_desc: planes 0/1 are Ex/Ey, 3 planes out */
+  float dx, dy;
+  int Z;                    /* 1 .. THZ_MAX_Z */
+  const float* z;           /* host [Z] */
+  const float* wavelengths; /* host [C] */
+  int row;                  /* 0 <= row < Ph - H */
+} thz_rsc_slice_desc;
+
+int thz_rsc_slice_workspace_size(const thz_rsc_slice_desc* d, size_t* bytes);
+int thz_rsc_slice_forward(const thz_rsc_slice_desc* d, const void* in /* [B,C,H,W] */,
+                          void* out /* [Z,Bo,C,Pw-W] */, void* workspace, size_t workspace_bytes,
+                          thz_stream_t stream);
 
 /* The Rayleigh-Sommerfeld kernel exp(i k r) z / (2 pi r^2) (1/r - i k), r = sqrt(x^2 + y^2 + z^2),
  * k = 2 pi / lambda_c, on n mesh points: CZT_prop.RS_kernel (Props/CZT_Prop.py:44-57) and the
@@ -596,7 +641,8 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * duration and launch count for one kernel name ("asm_rows_fwd", "asm_cols", "asm_rows_inv"; the
  * z-x slice: "asm_rows_fwd", "asm_cols_slice", "asm_rows_slice"; its adjoint: "asm_rows_fwd",
  * "asm_cols_slice_adj", "asm_rows_inv"; the CZT z-x slice: "czt_slice_tables", "czt_slice_collapse",
- * "czt_slice_line"; its adjoint: "czt_slice_tables", "czt_slice_line_adj", "czt_slice_expand"; ...).
+ * "czt_slice_line"; its adjoint: "czt_slice_tables", "czt_slice_line_adj", "czt_slice_expand"; the
+ * RSC z-x slice: "rsc_slice_rows", "rsc_slice_acc", "rsc_slice_line"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

@@ -26,6 +26,16 @@ def _f(v):
     return float(v.detach().cpu()) if torch.is_tensor(v) else float(v)
 
 
+def _z_host(z):
+    """The plane distances of a z-sweep as host floats (a tensor, a sequence or one value)."""
+    if torch.is_tensor(z):
+        return [float(v) for v in z.detach().reshape(-1).cpu().tolist()]
+    try:
+        return [_f(v) for v in z]
+    except TypeError:
+        return [float(z)]
+
+
 class RSC_prop(nn.Module):
     _vectorial = False
 
@@ -100,12 +110,15 @@ class RSC_prop(nn.Module):
             self.check_Zc = False
         return _prop.rs_kernel(self.meshx, self.meshy, self._zh, wl)
 
-    def forward(self, field: ElectricField) -> ElectricField:
-        data = field.data
-        B, C, H, W = self.shape = data.shape
+    def _single_field(self, B):
         if not self._vectorial and B != 1:
             raise RuntimeError(f"RSC_prop convolves a single field (B == 1) as the reference does "
                                f"(Props/RSC_Prop.py:198-200); got B={B}")
+
+    def forward(self, field: ElectricField) -> ElectricField:
+        data = field.data
+        B, C, H, W = self.shape = data.shape
+        self._single_field(B)
         sp = field.spacing_host
         wl = field.wavelengths_host
         if self.check_Zc:
@@ -115,6 +128,65 @@ class RSC_prop(nn.Module):
         out = _RscFunction.apply(x, tuple(wl), tuple(sp), self._zh, self._vectorial)
         Eout = ElectricField(data=out, wavelengths=field.wavelengths, spacing=field.spacing, device=field.device)
         return Eout._adopt_host(field)
+
+    def propagate_planes(self, field: ElectricField, z_list) -> torch.Tensor:
+        """Additive API: the planes of ``z_list`` -> [Z, Bo, C, Ho, Wo], ``forward`` per plane (the same
+        kernels, differentiable) stacked; the instance's own ``z`` is not touched.  The counterpart of
+        ASM_prop / CZT_prop.propagate_planes, and the fallback and yardstick of propagate_zx."""
+        self._single_field(field.data.shape[0])
+        x = _prop.kernel_dtype(field.data, "RSC_prop", field.wavelengths)
+        wl, sp = tuple(field.wavelengths_host), tuple(field.spacing_host)
+        return torch.stack([_RscFunction.apply(x, wl, sp, zh, self._vectorial) for zh in _z_host(z_list)])
+
+    def propagate_zx(self, field: ElectricField, z_list, row=None, axis="x") -> torch.Tensor:
+        """Additive API: one output row of every plane of ``z_list`` -> [Z, Bo, C, Wo], equal to
+        ``propagate_planes(field, z_list)[..., row, :]`` -- the x-z cross-section of a focal region on
+        the Rayleigh-Sommerfeld convolution, which otherwise costs one ``forward`` per plane.  ``row``
+        indexes the Ho = 2 (H // 2) output rows; None is the centre row Ho // 2.  ``axis="y"`` returns
+        ``planes[..., :, row]`` instead, [Z, Bo, C, Ho], ``row`` then indexing the Wo output columns.
+        ``z_list`` may have any length (chunks of THZ_MAX_Z planes).
+
+        A complex64 device field that does not require grad (or under ``no_grad``) runs the slice
+        kernels (thz_rsc_slice_forward): the input rows' spectra once, then per plane H kernel rows
+        evaluated, transformed and accumulated, and one inverse line per (z, b, c) -- no transform
+        along H, no Ph x Pw kernel table.  ``axis="y"`` runs them on the transposed field with the
+        spacing unchanged: the kernel's grid takes dx on both axes (Props/RSC_Prop.py:83-84) and
+        dx dy is symmetric, so the exchange is exact; for VRS the Ex / Ey planes are exchanged going in
+        and output planes 0 / 1 coming out (Ez = Ex x / r + Ey y / r is symmetric under the exchange).
+        A complex128 field or an input that requires grad propagates the full planes and slices them,
+        which keeps the fp64 kernels and autograd."""
+        if axis not in ("x", "y"):
+            raise ValueError(f"propagate_zx: axis must be 'x' or 'y', got {axis!r}")
+        B, C, H, W = field.data.shape
+        Ho, Wo = 2 * (H // 2), 2 * (W // 2)
+        n = Ho if axis == "x" else Wo
+        if row is None:
+            row = n // 2
+        row = int(row)
+        if not 0 <= row < n:
+            raise ValueError(f"propagate_zx: row {row} outside the valid range [0, {n}) of the output "
+                             f"{'rows' if axis == 'x' else 'columns'}")
+        self._single_field(B)
+        zs = _z_host(z_list)
+        x = _prop.kernel_dtype(field.data, "RSC_prop", field.wavelengths)
+        if x.dtype == torch.complex64 and x.is_cuda and not (torch.is_grad_enabled() and x.requires_grad):
+            wl, sp = tuple(field.wavelengths_host), tuple(field.spacing_host)
+            xs = x.detach()
+            if axis == "y":
+                xs = xs.transpose(-1, -2)
+                if self._vectorial:
+                    xs = xs[[1, 0]]
+            xs = xs.contiguous()
+            max_z = _prop._lib.THZ_MAX_Z
+            Bo = 3 if self._vectorial else B
+            out = torch.empty((len(zs), Bo, C, Wo if axis == "x" else Ho), dtype=torch.complex64, device=x.device)
+            for k in range(0, len(zs), max_z):
+                _prop.rsc_slice_apply(xs, wl, sp, zs[k:k + max_z], row, self._vectorial, out=out[k:k + max_z])
+            if axis == "y" and self._vectorial:
+                out = out[:, [1, 0, 2]]
+            return out
+        planes = self.propagate_planes(field, zs)
+        return planes[..., row, :] if axis == "x" else planes[..., :, row]
 
 
 class VRS_prop(RSC_prop):

@@ -35,6 +35,7 @@ EXPORTED = [
     "thz_czt_slice_workspace_size", "thz_czt_slice_forward",
     "thz_czt_slice_adjoint_workspace_size", "thz_czt_slice_adjoint",
     "thz_rsc_workspace_size", "thz_rsc_forward",
+    "thz_rsc_slice_workspace_size", "thz_rsc_slice_forward",
     "thz_doe_modulate_forward", "thz_doe_modulate_backward", "thz_quant_forward", "thz_quant_backward",
     "thz_doe_quant_backward", "thz_radial_quant_backward",
     "thz_radial_forward", "thz_radial_backward",
@@ -94,6 +95,15 @@ class RscDesc(ctypes.Structure):
         ("B", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
         ("vectorial", ctypes.c_int), ("dx", ctypes.c_float), ("dy", ctypes.c_float), ("z", ctypes.c_float),
         ("wavelengths", ctypes.POINTER(ctypes.c_float)), ("adjoint", ctypes.c_int),
+    ]
+
+
+class RscSliceDesc(ctypes.Structure):
+    _fields_ = [
+        ("B", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+        ("vectorial", ctypes.c_int), ("dx", ctypes.c_float), ("dy", ctypes.c_float),
+        ("Z", ctypes.c_int), ("z", ctypes.POINTER(ctypes.c_float)),
+        ("wavelengths", ctypes.POINTER(ctypes.c_float)), ("row", ctypes.c_int),
     ]
 
 
@@ -230,6 +240,9 @@ def _declare(lib):
     lib.thz_fft_rows.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
     lib.thz_rsc_workspace_size.argtypes = [ctypes.POINTER(RscDesc), ctypes.POINTER(c_size_t)]
     lib.thz_rsc_forward.argtypes = [ctypes.POINTER(RscDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_rsc_slice_workspace_size.argtypes = [ctypes.POINTER(RscSliceDesc), ctypes.POINTER(c_size_t)]
+    lib.thz_rsc_slice_forward.argtypes = [ctypes.POINTER(RscSliceDesc), c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]
     lib.thz_doe_modulate_forward.argtypes = [ctypes.POINTER(DoeDesc), c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p]
     lib.thz_doe_modulate_backward.argtypes = [ctypes.POINTER(DoeDesc), c_void_p, c_void_p, c_void_p, c_void_p,

@@ -683,3 +683,30 @@ def rsc_apply(data, wavelengths, spacing, z, vectorial=False, adjoint=False, fie
         return out.zero_()
     _launch(size_fn, run_fn, d, data.device, data, out)
     return out
+
+
+def rsc_slice_apply(data, wavelengths, spacing, zs, row, vectorial=False, out=None):
+    """Raw launch of the RSC / VRS z-x slice (thz_rsc_slice_forward): data [B,C,H,W] complex64 ->
+    [Z,Bo,C,Pw-W], output row ``row`` of every plane of ``zs`` (at most THZ_MAX_Z), equal to
+    rsc_apply(..., z, vectorial)[:, :, row, :] per z without forming the planes or the kernel's
+    2-D spectrum.  Forward only."""
+    _require_device(data, "RSC slice")
+    if data.dtype != torch.complex64:
+        raise TypeError(f"RSC slice kernels compute in complex64; got {data.dtype}")
+    L = _lib.lib()
+    data = data.contiguous()
+    B, C, H, W = data.shape
+    wl = _lib.float_array(wavelengths)
+    zv = _lib.float_array(zs)
+    d = _lib.RscSliceDesc(B=B, C=C, H=H, W=W, vectorial=int(bool(vectorial)), dx=float(spacing[0]),
+                          dy=float(spacing[1]), Z=len(zs), z=ctypes.cast(zv, ctypes.POINTER(ctypes.c_float)),
+                          wavelengths=ctypes.cast(wl, ctypes.POINTER(ctypes.c_float)), row=int(row))
+    shape = (len(zs), 3 if vectorial else B, C, 2 * (W // 2))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex64, device=data.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.complex64 or not out.is_contiguous():
+        raise ValueError(f"RSC slice: out must be a contiguous complex64 {shape} tensor")
+    if out.numel() == 0:  # W = 1: the reference's [..., W:] window is empty
+        return out
+    _launch(L.thz_rsc_slice_workspace_size, L.thz_rsc_slice_forward, d, data.device, data, out)
+    return out
