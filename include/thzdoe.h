@@ -58,7 +58,8 @@ typedef void* thz_stream_t; /* hipStream_t */
  * are purely additive, so the version stays 9 -- a caller detects them by symbol; likewise
  * thz_czt_slice_workspace_size and thz_czt_slice_forward with their own new thz_czt_slice_desc, and
  * thz_czt_slice_adjoint_workspace_size and thz_czt_slice_adjoint on the same descriptor, and
- * thz_rsc_slice_workspace_size and thz_rsc_slice_forward with their new thz_rsc_slice_desc):
+ * thz_rsc_slice_workspace_size and thz_rsc_slice_forward with their new thz_rsc_slice_desc, and
+ * thz_rsc_slice_adjoint_workspace_size and thz_rsc_slice_adjoint on the same descriptor):
  * a caller compares thz_abi_version()
  * with the THZ_ABI_VERSION it was compiled against before its first call, since a shorter
  * struct from an older header would make the library read past it.  Descriptors are plain C
@@ -299,7 +300,7 @@ int thz_rsc_forward(const thz_rsc_desc* d, const void* in, void* out, void* work
  * rows, in registers) and one line launch (the hs partials added in index order, one inverse Pw-point
  * transform per (k, b, c), x dx dy / Pw, elements [W, Pw)).  No transform along H, no Ph x Pw kernel
  * table or its 2-D FFT; two calls with the same inputs are bit-identical (fixed split, fixed order,
- * no atomics).  Forward only, host z[] only.
+ * no atomics).  Forward only (the adjoint is thz_rsc_slice_adjoint below), host z[] only.
  * Validation, all before any device call: the shape rules of thz_rsc_forward (THZ_E_ARG for a bad
  * shape, vectorial with B < 2 or null wavelengths; THZ_E_UNSUPPORTED for C > THZ_MAX_WAVELENGTHS or a
  * grid past the longest transform); a bad row, Z outside 1 .. THZ_MAX_Z or a null pointer THZ_E_ARG; a
@@ -323,6 +324,35 @@ typedef struct thz_rsc_slice_desc {
 int thz_rsc_slice_workspace_size(const thz_rsc_slice_desc* d, size_t* bytes);
 int thz_rsc_slice_forward(const thz_rsc_slice_desc* d, const void* in /* [B,C,H,W] */,
                           void* out /* [Z,Bo,C,Pw-W] */, void* workspace, size_t workspace_bytes,
+                          thz_stream_t stream);
+/*
+ * Adjoint of the RSC / VRS z-x slice (the autograd backward of thz_rsc_slice_forward), same descriptor:
+ *   grad_out [Z, Bo, C, Pw - W] -> grad_in [B, C, H, W] = sum over k of A_{z_k,row}^H grad_out[k]
+ * With Kh_{k,c,i} = FFT_Pw(RS_{z_k,c}(x[H + row - i], y[:])), the forward's kernel rows, per chunk of
+ * zc = min(Z, 32) planes:
+ *   Gh[k,b,c,:]  = dx dy / Pw FFT_Pw(grad_out[k,b,c,:] placed at [W, Pw), zeros before)   one line per (k, b, c)
+ *   S[b,c,i,m]  += sum over the chunk's k of conj(Kh_{k,c,i}[m]) Gh[k,b,c,m]              one kernel-row transform
+ *                                                                 per (k, c, i), serving every b, as the forward
+ * and after the last chunk grad_in[b,c,i,j] = IFFT_Pw(S[b,c,i,:])[j], j < W, unnormalised.  The planes
+ * are summed in the spectrum: one inverse transform per input row, whatever Z.  VRS (Ez = Ex x/r_k +
+ * Ey y/r_k carries the plane's z in r_k): output planes 0 / 1 as above; the third plane's product rows
+ * are kept per plane of the chunk, inverted, multiplied by x_i / r_k and y_j / r_k and added to
+ * grad_in[0] and grad_in[1] by the lane that owns the element, in plane order; the summed rows are
+ * added last.  The first chunk stores S and the VRS terms (grad_in may be uninitialised memory; every
+ * element is written), later chunks read, add and store on the same stream: no memset, no atomics, a
+ * fixed summation order, so two calls with the same inputs are bit-identical; no transform along H,
+ * no Ph x Pw table.  (W = 1: grad_out is empty and grad_in is set to zero, the one memset.)
+ * Purely additive: THZ_ABI_VERSION stays 9, a caller detects the entries by symbol.  Validation is the
+ * forward's, all before any device call: its shape rules; a bad row, Z outside 1 .. THZ_MAX_Z or a
+ * null pointer THZ_E_ARG; a short or null workspace THZ_E_WORKSPACE (the message names the size).
+ * Workspace:
+ *   8 (vectorial ? 2 + zc : B) C H Pw      S, the summed spectra (VRS: Ex, Ey and the chunk's Ez product rows)
+ * + 8 zc Bo C Pw                           Gh, one chunk's cotangent lines
+ * bytes, each part rounded up to 256 -- no Ph x Pw table, no growth with Z past one chunk.
+ */
+int thz_rsc_slice_adjoint_workspace_size(const thz_rsc_slice_desc* d, size_t* bytes);
+int thz_rsc_slice_adjoint(const thz_rsc_slice_desc* d, const void* grad_out /* [Z,Bo,C,Pw-W] */,
+                          void* grad_in /* [B,C,H,W] */, void* workspace, size_t workspace_bytes,
                           thz_stream_t stream);
 
 /* The Rayleigh-Sommerfeld kernel exp(i k r) z / (2 pi r^2) (1/r - i k), r = sqrt(x^2 + y^2 + z^2),
@@ -642,7 +672,8 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * z-x slice: "asm_rows_fwd", "asm_cols_slice", "asm_rows_slice"; its adjoint: "asm_rows_fwd",
  * "asm_cols_slice_adj", "asm_rows_inv"; the CZT z-x slice: "czt_slice_tables", "czt_slice_collapse",
  * "czt_slice_line"; its adjoint: "czt_slice_tables", "czt_slice_line_adj", "czt_slice_expand"; the
- * RSC z-x slice: "rsc_slice_rows", "rsc_slice_acc", "rsc_slice_line"; ...).
+ * RSC z-x slice: "rsc_slice_rows", "rsc_slice_acc", "rsc_slice_line"; its adjoint: "rsc_slice_line_adj",
+ * "rsc_slice_acc_adj", "rsc_slice_rows_adj"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

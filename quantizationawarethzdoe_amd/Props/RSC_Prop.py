@@ -138,7 +138,7 @@ class RSC_prop(nn.Module):
         wl, sp = tuple(field.wavelengths_host), tuple(field.spacing_host)
         return torch.stack([_RscFunction.apply(x, wl, sp, zh, self._vectorial) for zh in _z_host(z_list)])
 
-    def propagate_zx(self, field: ElectricField, z_list, row=None, axis="x") -> torch.Tensor:
+    def propagate_zx(self, field: ElectricField, z_list, row=None, axis="x", grad="planes") -> torch.Tensor:
         """Additive API: one output row of every plane of ``z_list`` -> [Z, Bo, C, Wo], equal to
         ``propagate_planes(field, z_list)[..., row, :]`` -- the x-z cross-section of a focal region on
         the Rayleigh-Sommerfeld convolution, which otherwise costs one ``forward`` per plane.  ``row``
@@ -154,9 +154,20 @@ class RSC_prop(nn.Module):
         dx dy is symmetric, so the exchange is exact; for VRS the Ex / Ey planes are exchanged going in
         and output planes 0 / 1 coming out (Ez = Ex x / r + Ey y / r is symmetric under the exchange).
         A complex128 field or an input that requires grad propagates the full planes and slices them,
-        which keeps the fp64 kernels and autograd."""
+        which keeps the fp64 kernels and autograd.
+
+        ``grad`` chooses what serves a differentiated call, as on ASM_prop / CZT_prop.propagate_zx.
+        ``"planes"`` (the default) is the behaviour above.  ``"slice"``: the slice kernels serve a
+        complex64 device field whether or not it requires grad, and the backward is their own adjoint
+        (thz_rsc_slice_adjoint: one cotangent line transform per (z, b, c), the kernel rows' conjugated
+        spectra summed over the planes in the spectrum, one inverse row per (b, c, i); nothing of a
+        plane's size per z in either direction); ``axis="y"`` transposes and exchanges Ex / Ey outside
+        the slice (torch differentiates both).  A complex128 field still takes the full planes.  Any
+        other value is a ValueError."""
         if axis not in ("x", "y"):
             raise ValueError(f"propagate_zx: axis must be 'x' or 'y', got {axis!r}")
+        if grad not in ("planes", "slice"):
+            raise ValueError(f"propagate_zx: grad must be 'planes' or 'slice', got {grad!r}")
         B, C, H, W = field.data.shape
         Ho, Wo = 2 * (H // 2), 2 * (W // 2)
         n = Ho if axis == "x" else Wo
@@ -169,8 +180,17 @@ class RSC_prop(nn.Module):
         self._single_field(B)
         zs = _z_host(z_list)
         x = _prop.kernel_dtype(field.data, "RSC_prop", field.wavelengths)
-        if x.dtype == torch.complex64 and x.is_cuda and not (torch.is_grad_enabled() and x.requires_grad):
+        diff = torch.is_grad_enabled() and x.requires_grad
+        if x.dtype == torch.complex64 and x.is_cuda and not (diff and grad == "planes"):
             wl, sp = tuple(field.wavelengths_host), tuple(field.spacing_host)
+            if diff:  # grad="slice": the slice kernels forward, thz_rsc_slice_adjoint backward
+                xs = x
+                if axis == "y":
+                    xs = xs.transpose(-1, -2)
+                    if self._vectorial:
+                        xs = xs[[1, 0]]
+                out = _prop.rsc_propagate_zx(xs, wl, sp, zs, row, self._vectorial)
+                return out[:, [1, 0, 2]] if axis == "y" and self._vectorial else out
             xs = x.detach()
             if axis == "y":
                 xs = xs.transpose(-1, -2)

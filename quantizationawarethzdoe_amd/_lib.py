@@ -36,6 +36,7 @@ EXPORTED = [
     "thz_czt_slice_adjoint_workspace_size", "thz_czt_slice_adjoint",
     "thz_rsc_workspace_size", "thz_rsc_forward",
     "thz_rsc_slice_workspace_size", "thz_rsc_slice_forward",
+    "thz_rsc_slice_adjoint_workspace_size", "thz_rsc_slice_adjoint",
     "thz_doe_modulate_forward", "thz_doe_modulate_backward", "thz_quant_forward", "thz_quant_backward",
     "thz_doe_quant_backward", "thz_radial_quant_backward",
     "thz_radial_forward", "thz_radial_backward",
@@ -242,6 +243,9 @@ def _declare(lib):
     lib.thz_rsc_forward.argtypes = [ctypes.POINTER(RscDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.thz_rsc_slice_workspace_size.argtypes = [ctypes.POINTER(RscSliceDesc), ctypes.POINTER(c_size_t)]
     lib.thz_rsc_slice_forward.argtypes = [ctypes.POINTER(RscSliceDesc), c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]
+    lib.thz_rsc_slice_adjoint_workspace_size.argtypes = [ctypes.POINTER(RscSliceDesc), ctypes.POINTER(c_size_t)]
+    lib.thz_rsc_slice_adjoint.argtypes = [ctypes.POINTER(RscSliceDesc), c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p]
     lib.thz_doe_modulate_forward.argtypes = [ctypes.POINTER(DoeDesc), c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p]

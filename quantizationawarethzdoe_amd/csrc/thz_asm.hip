@@ -1702,6 +1702,184 @@ __global__ void __launch_bounds__(1024) rsc_slice_line(const float2* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
+// Adjoint of the RSC / VRS z-x slice (thz_rsc_slice_adjoint), the forward's three steps reversed:
+//   rsc_slice_line_adj : Gh[k][b C + c][:] = dx dy / Pw FFT_Pw(g[k,b,c,:] placed at [W, Pw)), per (k, b, c)
+//   rsc_slice_acc_adj  : per (c, input row i, tile of b): for every plane of the chunk the kernel row
+//                        -> FFT in LDS -> conj x Gh[k,b,c,:], summed over the planes in index order
+//                        -> S[b][c][i][:] (the first chunk stores, later chunks read, add and store);
+//                        VRS's third plane keeps its product rows per plane, S[2 + k][c][i][:]
+//   rsc_slice_rows_adj : inverse FFT of the S rows, elements [0, W) -> grad_in; VRS's Ez rows per
+//                        chunk, x x/r_k and y/r_k, added into grad_in[0] / grad_in[1] by the owning lane
+// The same kernel values, transforms and grids as the forward; every sum in a fixed order.
+// ---------------------------------------------------------------------------------------------
+template <int PN>
+__global__ void __launch_bounds__(1024) rsc_slice_line_adj(const float2* __restrict__ g, float2* __restrict__ Gh,
+                                                          FftPlan pw, RscSliceArgs a) {
+  extern __shared__ float2 lds[];
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int Wo = a.Pw - a.W;
+  const float2* src = g + ((size_t)a.zoff * a.Bo * a.C + blockIdx.x) * Wo;
+  float2* dst = Gh + (size_t)blockIdx.x * a.Pw;
+  auto load = [&](int j) { return j >= a.W ? src[j - a.W] : make_float2(0.f, 0.f); };
+  if constexpr (PN > 0) {
+    const TwLds twl = load_tw_lds<PN>(tw_slot<PN>(lds), pw.tw, tid, nt);
+    auto ld = [&](int, int, int j) { return load(j); };
+    auto sv = [&](int, int, int j, float2 v) { dst[j] = cscale(v, a.scale); };
+    fft_pow2_run<false, PN, Geo<PN>::T, FFT_ROWS>(lds, twl, tid, ld, sv);
+  } else {
+    for (int j = tid; j < a.Pw; j += nt) lds[padx(j)] = load(j);
+    __syncthreads();
+    fft_lds<false>(lds, pw, tid, nt);
+    for (int j = tid; j < a.Pw; j += nt) dst[j] = cscale(lds[padx(j)], a.scale);
+  }
+}
+
+// One workgroup per (c, i, tile of b); the sums over the chunk's planes live where rsc_slice_acc
+// holds its sums over the rows: in registers on the compile-time plans, in the workgroup's own S rows
+// (each element owned by one lane) on the runtime plan.  rss_acc_select picks both kernels alike.
+template <int PN, int BT>
+__global__ void __launch_bounds__(rss_threads_max<PN>()) rsc_slice_acc_adj(const float2* __restrict__ Gh,
+                                                                          float2* __restrict__ S, FftPlan pw,
+                                                                          RscSliceArgs a) {
+  constexpr bool REG = PN > 0;
+  static_assert(PN == 0 || rss_acc_compiled(PN), "compile-time plans: 1024 .. 8192");
+  static_assert(BT >= 1 && BT <= (REG ? RSS_BT_MAX : 1), "the sums in S: one plane per workgroup");
+  extern __shared__ float2 lds[];
+  const int tid = threadIdx.x, nt = blockDim.x;
+  int id = blockIdx.x;
+  const int bt = id % a.nbt; id /= a.nbt;
+  const int i = id % a.H, c = id / a.H;
+  const float lam = a.lam[c];
+  const float kw = 6.283185307179586f / lam;
+  const float xlo = -(float)a.Ph * a.dx / 2.0f, xhi = (float)a.Ph * a.dx / 2.0f;
+  const float ylo = -(float)a.Pw * a.dx / 2.0f, yhi = (float)a.Pw * a.dx / 2.0f;
+  const float xi = lin(xlo, xhi, a.Ph, a.H + a.row - i);
+  const bool first = a.zoff == 0;  // the first chunk stores S
+  const int b0 = bt * BT;
+  const size_t prow = (size_t)a.H * a.Pw, off = ((size_t)c * a.H + i) * a.Pw;
+  const float2* grow[BT];  // a tile's planes past Bo read plane Bo - 1 and are not stored
+  float2* srow[BT];        // the summed row; VRS's third plane: its row of chunk plane 0
+  bool ez[BT];
+#pragma unroll
+  for (int t = 0; t < BT; ++t) {
+    const int b = min(b0 + t, a.Bo - 1);
+    ez[t] = a.vec && b == 2;
+    grow[t] = Gh + (size_t)(b * a.C + c) * a.Pw;
+    srow[t] = S + (size_t)b * a.C * prow + off;
+  }
+  const size_t gstep = (size_t)a.Bo * a.C * a.Pw, estep = (size_t)a.C * prow;  // per chunk plane
+  float2 acc[BT][16];
+#pragma unroll
+  for (int t = 0; t < BT; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[t][q] = make_float2(0.f, 0.f);
+  // element j of chunk plane kk's conjugated kernel-row spectrum times the cotangent lines, slot q
+  auto add = [&](int kk, int q, int j, float2 v) {
+#pragma unroll
+    for (int t = 0; t < BT; ++t) {
+      const float2 w = cmulc(grow[t][kk * gstep + j], v);
+      if (ez[t]) srow[t][kk * estep + j] = w;
+      else if constexpr (REG) acc[t][q] = cadd(acc[t][q], w);
+      else srow[t][j] = (first && kk == 0) ? w : cadd(srow[t][j], w);
+    }
+  };
+  if constexpr (PN > 0) {
+    constexpr int TT = Geo<PN>::T;
+    using SC = Pow2Sched<PN>;
+    constexpr int RL = SC::radix(SC::nst(FFT_ROWS) - 1, FFT_ROWS);
+    const TwLds twl = load_tw_lds<PN>(tw_slot<PN>(lds), pw.tw, tid, nt);
+    for (int kk = 0; kk < a.nz; ++kk) {
+      const float z = a.zv[a.zoff + kk];
+      const RsPhase rph = rs_phase(lam, z);
+      auto ld = [&](int, int, int j) { return rs_kernel(xi, lin(ylo, yhi, PN, j), z, kw, rph); };
+      auto sv = [&](int m, int r, int j, float2 v) { add(kk, m * RL + r, j, v); };
+      fft_pow2_run<false, PN, TT, FFT_ROWS>(lds, twl, tid, ld, sv);
+    }
+#pragma unroll
+    for (int t = 0; t < BT; ++t) {
+      if (b0 + t >= a.Bo) break;
+      if (ez[t]) continue;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int j = tid + (q / RL) * TT + (q % RL) * (PN / RL);
+        srow[t][j] = first ? acc[t][q] : cadd(srow[t][j], acc[t][q]);
+      }
+    }
+  } else {
+    for (int kk = 0; kk < a.nz; ++kk) {
+      const float z = a.zv[a.zoff + kk];
+      const RsPhase rph = rs_phase(lam, z);
+      __syncthreads();  // the previous plane's reads of the image are done
+      for (int j = tid; j < a.Pw; j += nt) lds[padx(j)] = rs_kernel(xi, lin(ylo, yhi, a.Pw, j), z, kw, rph);
+      __syncthreads();
+      fft_lds<false>(lds, pw, tid, nt);
+      for (int j = tid; j < a.Pw; j += nt) add(kk, 0, j, lds[padx(j)]);
+    }
+  }
+}
+
+// The adjoint of vrs_ez: what a cotangent e of Ez adds to those of Ex and Ey, rounded as vrs_ez rounds.
+#pragma clang fp contract(off)
+__device__ __forceinline__ void vrs_ez_adj(float2 e, float x, float y, float z, float2& gx, float2& gy) {
+  const float r = sqrtf(x * x + y * y + z * z);
+  gx = make_float2((e.x * x) / r, (e.y * x) / r);
+  gy = make_float2((e.x * y) / r, (e.y * y) / r);
+}
+#pragma clang fp contract(on)
+
+// EZ false: one workgroup per (plane u, c, i) of the summed S rows, after the last chunk: the inverse
+// transform's elements [0, W) are stored to grad_in (VRS: added to the Ez terms already there).
+// EZ true (VRS, once per chunk): one workgroup per (c, i) runs the chunk's Ez product rows in plane
+// order, each lane adding its own elements x x/r_k, y/r_k into grad_in[0], grad_in[1]; the call's
+// first plane stores them.  With the two divisions per element the Ez form needs more than the 128
+// VGPRs of a 1024-lane workgroup: it is instantiated where rsc_slice_acc_adj is (at most 512 lanes on
+// the compile-time plans, Pw = 16384 on the runtime plan) and chosen with it by rss_acc_select.
+template <int PN, bool EZ>
+__global__ void __launch_bounds__(EZ ? rss_threads_max<PN>() : 1024) rsc_slice_rows_adj(const float2* __restrict__ S, float2* __restrict__ gin,
+                                                          FftPlan pw, RscSliceArgs a) {
+  extern __shared__ float2 lds[];
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int i = blockIdx.x % a.H, c = (blockIdx.x / a.H) % a.C, u = EZ ? 2 : blockIdx.x / (a.H * a.C);
+  const size_t prow = (size_t)a.C * a.H * a.Pw;  // one plane of S
+  const float2* src = S + u * prow + ((size_t)c * a.H + i) * a.Pw;
+  float2* dst = gin + ((size_t)((EZ ? 0 : u) * a.C + c) * a.H + i) * a.W;
+  float2* dsty = gin + ((size_t)(a.C + c) * a.H + i) * a.W;  // EZ: the Ey row
+  const float xh = lin(-(float)a.H * a.dx / 2.0f, (float)a.H * a.dx / 2.0f, a.H, i);
+  const int nk = EZ ? a.nz : 1;
+  // element j < W of the inverse transform of chunk plane kk's row
+  auto put = [&](int kk, int j, float2 v) {
+    if constexpr (!EZ) {
+      dst[j] = a.vec ? cadd(dst[j], v) : v;
+    } else {
+      float2 gx, gy;
+      vrs_ez_adj(v, xh, lin(-(float)a.W * a.dx / 2.0f, (float)a.W * a.dx / 2.0f, a.W, j), a.zv[a.zoff + kk], gx, gy);
+      const bool st = a.zoff == 0 && kk == 0;
+      dst[j] = st ? gx : cadd(dst[j], gx);
+      dsty[j] = st ? gy : cadd(dsty[j], gy);
+      __builtin_amdgcn_sched_barrier(0);  // one element's divisions at a time
+    }
+  };
+  if constexpr (PN > 0) {
+    const TwLds twl = load_tw_lds<PN>(tw_slot<PN>(lds), pw.tw, tid, nt);
+    for (int kk = 0; kk < nk; ++kk) {
+      auto ld = [&](int, int, int j) { return src[kk * prow + j]; };
+      auto sv = [&](int, int, int j, float2 v) {
+        if (j < a.W) put(kk, j, v);
+      };
+      fft_pow2_run<true, PN, Geo<PN>::T, FFT_ROWS>(lds, twl, tid, ld, sv);
+    }
+  } else {
+    for (int kk = 0; kk < nk; ++kk) {
+      __syncthreads();  // the previous plane's reads of the image are done
+      for (int j = tid; j < a.Pw; j += nt) lds[padx(j)] = src[kk * prow + j];
+      __syncthreads();
+      fft_lds<true>(lds, pw, tid, nt);
+      for (int j = tid; j < a.W; j += nt) put(kk, j, lds[padx(j)]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Generic batched row FFT (building block / diagnostics)
 // ---------------------------------------------------------------------------------------------
 template <int PN>
@@ -1927,10 +2105,14 @@ static int ensure_lds_attr() {
                            (const void*)asm_rows_inv<PN>, (const void*)asm_rows_inv_loss<PN>,
                            (const void*)asm_rows_slice<PN>, (const void*)fft_rows_kernel<PN>,
                            (const void*)rsc_k_rows<PN>, (const void*)rsc_k_cols<PN>,
-                           (const void*)rsc_slice_rows<PN>, (const void*)rsc_slice_line<PN>});
-      if constexpr (PN == 0 || rss_acc_compiled(PN)) ks.push_back((const void*)rsc_slice_acc<PN, 1>);
+                           (const void*)rsc_slice_rows<PN>, (const void*)rsc_slice_line<PN>,
+                           (const void*)rsc_slice_line_adj<PN>, (const void*)rsc_slice_rows_adj<PN, false>});
+      if constexpr (PN == 0 || rss_acc_compiled(PN))
+        ks.insert(ks.end(), {(const void*)rsc_slice_acc<PN, 1>, (const void*)rsc_slice_acc_adj<PN, 1>,
+                             (const void*)rsc_slice_rows_adj<PN, true>});
       if constexpr (rss_acc_compiled(PN))
-        ks.insert(ks.end(), {(const void*)rsc_slice_acc<PN, 2>, (const void*)rsc_slice_acc<PN, 3>});
+        ks.insert(ks.end(), {(const void*)rsc_slice_acc<PN, 2>, (const void*)rsc_slice_acc<PN, 3>,
+                             (const void*)rsc_slice_acc_adj<PN, 2>, (const void*)rsc_slice_acc_adj<PN, 3>});
       if constexpr (PN == 8192) ks.push_back((const void*)asm_rows_inv_mid<PN>);
     };
     for_each_size(Pow2Sizes{}, planes);
@@ -2701,16 +2883,23 @@ constexpr int RSS_ZC = 32;  // planes per chunk of the accumulate / line launche
 // every other width runs the runtime plan, one plane per workgroup.
 struct RssAcc {
   void (*k)(const float2*, float2*, FftPlan, RscSliceArgs);
+  void (*adj)(const float2*, float2*, FftPlan, RscSliceArgs);  // rsc_slice_acc_adj of the same plan and tile
+  void (*ezr)(const float2*, float2*, FftPlan, RscSliceArgs);  // the adjoint's Ez rows on the same plan
   int threads, bt;
   size_t lds;
 };
 static RssAcc rss_acc_select(int Pw, int Bo) {
-  RssAcc r{rsc_slice_acc<0, 1>, fft_threads(Pw), 1, fft_lds_bytes(Pw)};
+  RssAcc r{rsc_slice_acc<0, 1>, rsc_slice_acc_adj<0, 1>, rsc_slice_rows_adj<0, true>, fft_threads(Pw), 1,
+           fft_lds_bytes(Pw)};
   on_listed(SizeList<1024, 2048, 4096, 8192>{}, Pw, [&](auto N) {
     static_assert(rss_acc_compiled(N()), "the instantiated accumulate kernels");
     const int nbt = (Bo + RSS_BT_MAX - 1) / RSS_BT_MAX;
     r.bt = (Bo + nbt - 1) / nbt;
     r.k = r.bt == 3 ? rsc_slice_acc<N(), 3> : r.bt == 2 ? rsc_slice_acc<N(), 2> : rsc_slice_acc<N(), 1>;
+    r.adj = r.bt == 3   ? rsc_slice_acc_adj<N(), 3>
+            : r.bt == 2 ? rsc_slice_acc_adj<N(), 2>
+                        : rsc_slice_acc_adj<N(), 1>;
+    r.ezr = rsc_slice_rows_adj<N(), true>;
     r.threads = N() / pow2_v(N());
     r.lds = fft_lds_bytes_io(N());
   });
@@ -2721,8 +2910,9 @@ struct RscSlicePlan {
   RscSliceArgs a;
   RssAcc acc;
   int zc;
-  size_t uh, p;
+  size_t uh, p, gh;  // the forward's Uh | P; the adjoint's S (Uh's shape and size) | Gh
   size_t total() const { return uh + p; }
+  size_t total_adj() const { return uh + gh; }
 };
 
 static int rsc_slice_plan(const thz_rsc_slice_desc* d, RscSlicePlan* p) {
@@ -2750,6 +2940,7 @@ static int rsc_slice_plan(const thz_rsc_slice_desc* d, RscSlicePlan* p) {
   const size_t nu = a.vec ? 2 + (size_t)p->zc : (size_t)d->B;
   p->uh = align256(nu * d->C * d->H * a.Pw * sizeof(float2));
   p->p = align256((size_t)p->zc * a.Bo * d->C * a.hs * a.Pw * sizeof(float2));
+  p->gh = align256((size_t)p->zc * a.Bo * d->C * a.Pw * sizeof(float2));
   return THZ_OK;
 }
 
@@ -2815,6 +3006,73 @@ extern "C" int thz_rsc_slice_forward(const thz_rsc_slice_desc* d, const void* in
       THZ_LAUNCH_CHECK();
       kt.stop();
     }
+  }
+  return THZ_OK;
+}
+
+extern "C" int thz_rsc_slice_adjoint_workspace_size(const thz_rsc_slice_desc* d, size_t* bytes) {
+  RscSlicePlan p;
+  int e = rsc_slice_plan(d, &p);
+  if (e) return e;
+  if (!bytes) return fail(THZ_E_ARG, "null bytes");
+  *bytes = p.total_adj();
+  return THZ_OK;
+}
+
+extern "C" int thz_rsc_slice_adjoint(const thz_rsc_slice_desc* d, const void* grad_out, void* grad_in,
+                                     void* workspace, size_t workspace_bytes, thz_stream_t stream) {
+  RscSlicePlan p;
+  int e = rsc_slice_plan(d, &p);
+  if (e) return e;
+  if (!grad_out || !grad_in) return fail(THZ_E_ARG, "null data pointer");
+  if ((e = check_workspace(workspace, workspace_bytes, p.total_adj()))) return e;
+  RscSliceArgs& a = p.a;
+  hipStream_t s = (hipStream_t)stream;
+  if (a.Pw == a.W) {  // W = 1: the cotangent is empty and its adjoint zero (the one memset of this entry)
+    THZ_HIP_CHECK(hipMemsetAsync(grad_in, 0, (size_t)a.B * a.C * a.H * a.W * sizeof(float2), s));
+    return THZ_OK;
+  }
+  FftPlan pw;
+  if ((e = get_plan(a.Pw, &pw)) || (e = ensure_lds_attr())) return e;
+  float2* S = (float2*)workspace;
+  float2* Gh = (float2*)((char*)workspace + p.uh);
+  const int th = threads_for(a.Pw);
+  const size_t lds = fft_lds_bytes_io(a.Pw);
+  for (int k0 = 0; k0 < d->Z; k0 += p.zc) {
+    a.zoff = k0;
+    a.nz = std::min(p.zc, d->Z - k0);
+    {
+      KernelTimer kt("rsc_slice_line_adj", s);
+      on_pow2(a.Pw, [&](auto N) {
+        hipLaunchKernelGGL(rsc_slice_line_adj<N()>, dim3(a.nz * a.Bo * a.C), dim3(th), lds, s,
+                           (const float2*)grad_out, Gh, pw, a);
+      });
+      THZ_LAUNCH_CHECK();
+      kt.stop();
+    }
+    {
+      KernelTimer kt("rsc_slice_acc_adj", s);
+      hipLaunchKernelGGL(p.acc.adj, dim3(a.C * a.H * a.nbt), dim3(p.acc.threads), p.acc.lds, s, (const float2*)Gh, S,
+                         pw, a);
+      THZ_LAUNCH_CHECK();
+      kt.stop();
+    }
+    if (a.vec) {  // the chunk's Ez rows into grad_in[0], grad_in[1]
+      KernelTimer kt("rsc_slice_rows_adj", s);
+      hipLaunchKernelGGL(p.acc.ezr, dim3(a.C * a.H), dim3(p.acc.threads), p.acc.lds, s, (const float2*)S,
+                         (float2*)grad_in, pw, a);
+      THZ_LAUNCH_CHECK();
+      kt.stop();
+    }
+  }
+  {  // the summed rows, after the last chunk
+    KernelTimer kt("rsc_slice_rows_adj", s);
+    on_pow2(a.Pw, [&](auto N) {
+      hipLaunchKernelGGL((rsc_slice_rows_adj<N(), false>), dim3((a.vec ? 2 : a.B) * a.C * a.H), dim3(th), lds, s,
+                         (const float2*)S, (float2*)grad_in, pw, a);
+    });
+    THZ_LAUNCH_CHECK();
+    kt.stop();
   }
   return THZ_OK;
 }

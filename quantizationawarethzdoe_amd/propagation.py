@@ -685,22 +685,31 @@ def rsc_apply(data, wavelengths, spacing, z, vectorial=False, adjoint=False, fie
     return out
 
 
+def _rsc_slice_desc(B, C, H, W, vectorial, spacing, wavelengths, zs, row):
+    """thz_rsc_slice_desc (the host arrays are kept alive by the descriptor)."""
+    wl = _lib.float_array(wavelengths)
+    zv = _lib.float_array(zs)
+    d = _lib.RscSliceDesc(B=int(B), C=int(C), H=int(H), W=int(W), vectorial=int(bool(vectorial)),
+                          dx=float(spacing[0]), dy=float(spacing[1]), Z=len(zs),
+                          z=ctypes.cast(zv, ctypes.POINTER(ctypes.c_float)),
+                          wavelengths=ctypes.cast(wl, ctypes.POINTER(ctypes.c_float)), row=int(row))
+    d._keep = (wl, zv)
+    return d
+
+
 def rsc_slice_apply(data, wavelengths, spacing, zs, row, vectorial=False, out=None):
     """Raw launch of the RSC / VRS z-x slice (thz_rsc_slice_forward): data [B,C,H,W] complex64 ->
     [Z,Bo,C,Pw-W], output row ``row`` of every plane of ``zs`` (at most THZ_MAX_Z), equal to
     rsc_apply(..., z, vectorial)[:, :, row, :] per z without forming the planes or the kernel's
-    2-D spectrum.  Forward only."""
+    2-D spectrum.  Forward only; rsc_propagate_zx is the differentiable form (backward:
+    rsc_slice_adjoint)."""
     _require_device(data, "RSC slice")
     if data.dtype != torch.complex64:
         raise TypeError(f"RSC slice kernels compute in complex64; got {data.dtype}")
     L = _lib.lib()
     data = data.contiguous()
     B, C, H, W = data.shape
-    wl = _lib.float_array(wavelengths)
-    zv = _lib.float_array(zs)
-    d = _lib.RscSliceDesc(B=B, C=C, H=H, W=W, vectorial=int(bool(vectorial)), dx=float(spacing[0]),
-                          dy=float(spacing[1]), Z=len(zs), z=ctypes.cast(zv, ctypes.POINTER(ctypes.c_float)),
-                          wavelengths=ctypes.cast(wl, ctypes.POINTER(ctypes.c_float)), row=int(row))
+    d = _rsc_slice_desc(B, C, H, W, vectorial, spacing, wavelengths, zs, row)
     shape = (len(zs), 3 if vectorial else B, C, 2 * (W // 2))
     if out is None:
         out = torch.empty(shape, dtype=torch.complex64, device=data.device)
@@ -710,3 +719,56 @@ def rsc_slice_apply(data, wavelengths, spacing, zs, row, vectorial=False, out=No
         return out
     _launch(L.thz_rsc_slice_workspace_size, L.thz_rsc_slice_forward, d, data.device, data, out)
     return out
+
+
+def rsc_slice_adjoint(g, wavelengths, spacing, zs, row, field_shape, vectorial=False, out=None):
+    """Raw launch of the RSC / VRS z-x slice's adjoint (thz_rsc_slice_adjoint): the cotangent g
+    [Z,Bo,C,2(W//2)] complex64 of rsc_slice_apply(x, ...) with x.shape = field_shape = (B,C,H,W) ->
+    [B,C,H,W], the sum over the planes of each plane's adjoint -- rsc_apply(g[k] placed at row ``row``
+    of a zero plane, adjoint=True) per z, summed (VRS: with the Ez chain of each plane's own r), without
+    forming a plane.  At most THZ_MAX_Z planes.  ``out``, when given, is a contiguous complex64
+    [B,C,H,W] tensor; every element of it is overwritten."""
+    _require_device(g, "RSC slice adjoint")
+    if g.dtype != torch.complex64:
+        raise TypeError(f"RSC slice kernels compute in complex64; got {g.dtype}")
+    L = _lib.lib()
+    g = g.contiguous()
+    B, C, H, W = (int(v) for v in field_shape)
+    gshape = (len(zs), 3 if vectorial else B, C, 2 * (W // 2))
+    if tuple(g.shape) != gshape:
+        raise ValueError(f"RSC slice adjoint: gradient {tuple(g.shape)} is not {list(gshape)}")
+    d = _rsc_slice_desc(B, C, H, W, vectorial, spacing, wavelengths, zs, row)
+    shape = (B, C, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex64, device=g.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.complex64 or not out.is_contiguous():
+        raise ValueError(f"RSC slice adjoint: out must be a contiguous complex64 {shape} tensor")
+    if g.numel() == 0:  # W = 1: the forward's window is empty and its adjoint zero
+        return out.zero_()
+    _launch(L.thz_rsc_slice_adjoint_workspace_size, L.thz_rsc_slice_adjoint, d, g.device, g, out)
+    return out
+
+
+class _RscSliceFunction(torch.autograd.Function):
+    """The RSC / VRS z-x slice with its native backward: forward rsc_slice_apply, backward
+    rsc_slice_adjoint.  A linear map: nothing is saved but the configuration."""
+
+    @staticmethod
+    def forward(ctx, data, wavelengths, spacing, zs, row, vectorial):
+        ctx.cfg = (wavelengths, spacing, zs, row, vectorial, tuple(data.shape))
+        return rsc_slice_apply(data, wavelengths, spacing, zs, row, vectorial)
+
+    @staticmethod
+    def backward(ctx, g):
+        wavelengths, spacing, zs, row, vectorial, shape = ctx.cfg
+        return rsc_slice_adjoint(g, wavelengths, spacing, zs, row, shape, vectorial), None, None, None, None, None
+
+
+def rsc_propagate_zx(data, wavelengths, spacing, zs, row, vectorial=False):
+    """Differentiable RSC / VRS z-x slice on the slice kernels, forward and backward: [B,C,H,W]
+    complex64 -> [Z,Bo,C,2(W//2)], output row ``row`` of every plane of ``zs`` (any length: chunks of
+    THZ_MAX_Z planes)."""
+    wl, sp, zs = list(map(float, wavelengths)), tuple(map(float, spacing)), list(map(float, zs))
+    outs = [_RscSliceFunction.apply(data, wl, sp, zs[k:k + _lib.THZ_MAX_Z], int(row), bool(vectorial))
+            for k in range(0, len(zs), _lib.THZ_MAX_Z)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
