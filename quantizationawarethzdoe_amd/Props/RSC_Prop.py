@@ -95,11 +95,32 @@ class RSC_prop(nn.Module):
         meshx, meshy = torch.meshgrid(grid(H), grid(W), indexing="ij")
         return meshx.to(device=self.device), meshy.to(device=self.device)
 
+    def _kernel_grid(self, H, W, dx):
+        """The grid the convolution kernels evaluate the RS kernel on: the same end points as
+        create_spatial_grid, each coordinate as ONE fp32 expression, start + step i below the middle
+        and end + step (i - (n - 1)) from it on (csrc/thz_dev.hpp lin()).  torch.linspace on the CPU
+        (the reference's meshes) adds the step per SIMD lane onto a rounded vector base, a second
+        rounding: about 40 % of its coordinates differ from these by one ulp, k ulp = 7.5e-4 rad at
+        the far end of a 16384-point line."""
+        def grid(n):
+            lo, hi = (np.float32(-n) * np.float32(_f(dx))) / np.float32(2), (np.float32(n) * np.float32(_f(dx))) / np.float32(2)
+            if n == 1:
+                return torch.tensor([float(lo)])
+            step = (hi - lo) / np.float32(n - 1)
+            i = np.arange(n)
+            low = i < n // 2
+            k = np.where(low, i, i - (n - 1)).astype(np.float32)
+            return torch.from_numpy(np.where(low, lo, hi).astype(np.float32) + step * k)
+        meshx, meshy = torch.meshgrid(grid(H), grid(W), indexing="ij")
+        return meshx.to(device=self.device), meshy.to(device=self.device)
+
     def create_kernel(self, field: ElectricField) -> torch.Tensor:
         """The spatial RS kernel exp(ikr) z/(2 pi r^2)(1/r - ik) on the padded grid, [1, C, Ph, Pw]
         (Props/RSC_Prop.py:129-167), with the once-per-instance minimum-distance print.  The
         convolution kernels take FFT2 of the same values in-kernel; this materialises them with
-        thz_rs_kernel for inspection and sets ``meshx`` / ``meshy`` as the reference does."""
+        thz_rs_kernel for inspection, on the kernels' own grid (_kernel_grid), so the table is what
+        the propagation applies (tests/test_table_parity_gpu.py), and sets ``meshx`` / ``meshy`` as
+        the reference does (torch.linspace: equal to the kernels' grid to one ulp)."""
         B, C, H, W = field.shape
         Ph, Pw = self.compute_padding(H, W)
         sp, wl = field.spacing_host, field.wavelengths_host
@@ -108,7 +129,7 @@ class RSC_prop(nn.Module):
             self.shape = field.shape
             self.check_RS_minimum_z(1, sp[0], sp[1], min(wl), Ph=Ph)
             self.check_Zc = False
-        return _prop.rs_kernel(self.meshx, self.meshy, self._zh, wl)
+        return _prop.rs_kernel(*self._kernel_grid(Ph, Pw, sp[0]), self._zh, wl)
 
     def _single_field(self, B):
         if not self._vectorial and B != 1:

@@ -143,7 +143,9 @@ def test_asm_create_kernel_random_geometries_vs_oracle_masks():
 
 def test_asm_kernel_is_what_forward_applies():
     """The exported table is the transfer function the propagation kernels apply on the fly:
-    crop(ifft2(fft2(pad x) * ifftshift(H))) with torch's FFT on the exported H equals forward(x)."""
+    crop(ifft2(fft2(pad x) * ifftshift(H))) with torch's FFT on the exported H equals forward(x).
+    One field on the runtime plan against an fp32 GPU FFT; tests/test_table_parity_gpu.py builds this
+    comparison out (every plan family and entry point, fp64 CPU algebra, the fp32 FFT floor as bound)."""
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(3)
     x = torch.randn(1, 2, 48, 48, dtype=torch.complex64, generator=g).to(dev)
