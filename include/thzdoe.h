@@ -163,6 +163,14 @@ int thz_asm_slice_adjoint(const thz_asm_desc* d, int row, const void* grad_out /
 /* Plan facts for diagnostics / bench byte counts: number of spectral columns the kernels
  * keep (|m_y| <= J; ncols = 2J+1, or Pw when nothing is cut) and z-planes per column pass. */
 int thz_asm_band(const thz_asm_desc* d, int* ncols, int* z_chunk);
+/* Diagnostics (process-wide, like thz_timing_enable; purely additive, THZ_ABI_VERSION stays 9): which
+ * form of the inverse row pass the plain power-of-two ASM pipelines run from the next call on.
+ *   -1 the library's choice (the default: row pairs where they were measured faster, the middle-half
+ *      crop of a 8192-point row), 0 one output row per workgroup, 1 two rows per workgroup at every
+ *      power-of-two row length 1024 .. 16384.
+ * Both forms give bit-identical planes (tests/test_asm_rows_pair_gpu.py compares them); the fused-loss
+ * and mixed-radix row passes have one form and ignore the setting.  Another mode: THZ_E_ARG. */
+int thz_asm_row_pairs(int mode);
 /* The transfer function the ASM kernels apply on the fly, materialised for inspection:
  * ASM_prop.create_kernel (Props/ASM_Prop.py:212-311; used by visualize_kernel, :198-210).
  * out [C, Ph, Pw] complex64 (device) on the CENTRED frequency grid of the padded plane

@@ -27,7 +27,7 @@ BANDLIMIT = {None: 0, False: 0, "none": 0, "exact": 1, "approx": 2}
 # every symbol include/thzdoe.h declares (checked by tests/test_abi.py)
 EXPORTED = [
     "thz_version", "thz_last_error", "thz_abi_version",
-    "thz_asm_workspace_size", "thz_asm_forward", "thz_asm_band", "thz_asm_forward_modulated",
+    "thz_asm_workspace_size", "thz_asm_forward", "thz_asm_band", "thz_asm_row_pairs", "thz_asm_forward_modulated",
     "thz_asm_forward_loss", "thz_asm_adjoint_loss", "thz_asm_transfer_function", "thz_rs_kernel",
     "thz_asm_slice_workspace_size", "thz_asm_slice_forward",
     "thz_asm_slice_adjoint_workspace_size", "thz_asm_slice_adjoint",
@@ -286,6 +286,7 @@ def _declare(lib):
     lib.thz_fft64_rows.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
     lib.thz_step_fetch.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.thz_adam_step.argtypes = [ctypes.POINTER(AdamDesc), ctypes.POINTER(AdamParam), c_void_p]
+    lib.thz_asm_row_pairs.argtypes = [c_int]
     lib.thz_timing_enable.argtypes = [c_int]
     lib.thz_timing_reset.argtypes = []
     lib.thz_timing_read.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
@@ -324,6 +325,11 @@ def version():
 
 def timing_enable(on=True):
     check(lib().thz_timing_enable(int(bool(on))))
+
+
+def asm_row_pairs(mode=-1):
+    """Form of the ASM inverse row pass: -1 the library's choice, 0 one row, 1 two rows per workgroup."""
+    check(lib().thz_asm_row_pairs(int(mode)))
 
 
 def timing_reset():

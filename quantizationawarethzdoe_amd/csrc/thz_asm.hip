@@ -20,6 +20,7 @@
 // The adjoint (autograd backward) is the same pipeline with conj(H) and the input and
 // output windows exchanged.
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <cmath>
@@ -1150,6 +1151,66 @@ __global__ void __launch_bounds__(1024) THZ_ROW_ATTR asm_rows_inv_loss(const flo
   rows_inv_body<PN, true>(U, out, pw, a);
 }
 
+// K3 on row pairs (power-of-two sizes, no loss sums): one workgroup runs rows 2i and 2i + 1 of one
+// plane through the two-line transform (fft_pow2_run2), so the band tests, the gather and store
+// address math, every twiddle read, the table fill and the barriers are paid once per pair.  Both
+// rows lie in one 4-row U tile: the pair of a column is 16 contiguous, 16-B aligned bytes and comes
+// in one load.  The last workgroup of a plane with an odd Hout has one row: its line 1 transforms
+// zeros and stores nothing (a workgroup-uniform select at the loads and the stores; every thread
+// runs every barrier).  Each row's arithmetic is rows_inv_body's, bit for bit.
+template <int PN, bool MID>
+__device__ __forceinline__ void rows_inv_pair_body(const float2* __restrict__ U, float2* __restrict__ out, FftPlan pw,
+                                                   const AsmArgs& a) {
+  static_assert(PN >= 1024 && !is_mx(PN), "power-of-two sizes");
+  static_assert(URT % 2 == 0, "rows 2i and 2i + 1 share a U tile");
+  extern __shared__ float2 lds[];
+  constexpr int TT = Geo<PN>::T;
+  const int hp = (a.Hout + 1) >> 1;                    // row pairs per plane
+  const int pr = xcd_rows(blockIdx.x, gridDim.x);      // pair in [0, nz*BC*hp)
+  const int plane = pr / hp, r = 2 * (pr - plane * hp);  // plane = zz*BC + bc
+  const bool two = r + 1 < a.Hout;                     // workgroup-uniform
+  const int tid = threadIdx.x;
+  __builtin_assume(tid >= 0 && tid < TT);
+  const float2* src = U + (size_t)plane * a.ncbu * CBU * u_rows(a.Hout);
+  float2* dst0 = out + ((size_t)(a.zoff * a.BC + plane) * a.Hout + r) * a.Wout;
+  float2* dst1 = dst0 + a.Wout;
+  const auto twf = tw_fetch<PN, TT>(pw.tw, tid);
+  const TwLds twl = tw_lds_at<PN>(tw_slot2<PN>(lds));
+  auto tw_hook = [&]() { tw_store<PN, TT>(tw_slot2<PN>(lds), twf, tid); };
+  // the gather of rows_inv_body; row r is even, so (r, r + 1) of a column are one aligned float4
+  // (U's rows are padded to whole tiles: the load stays inside the plane for the one-row tail)
+  constexpr int NB0 = PN / pow2_v(PN);
+  static_assert(NB0 % CBU == 0, "band offsets must be whole U blocks");
+  static_assert(Geo<PN>::T == NB0 && NB0 == PN / 16, "radix-16 first stage, one butterfly per thread");
+  const int c0 = tid + a.J;
+  const float2* base = src + blk_u(c0, r, a.Hout);
+  const long cstride = u_rows(a.Hout);
+  const bool mid0 = __all(c0 + 4 * NB0 >= a.ncols && c0 + 11 * NB0 - PN < 0);
+  auto ld = [&](int, int q, int, float2& x0, float2& x1) {
+    x0 = x1 = make_float2(0.f, 0.f);
+    if (q >= 4 && q < 12 && mid0) return;
+    const int delta = q * NB0 >= PN / 2 ? q * NB0 - PN : q * NB0;
+    if ((unsigned)(c0 + delta) >= (unsigned)a.ncols) return;
+    const float4 x = *reinterpret_cast<const float4*>(base + (long)delta * cstride);
+    x0 = make_float2(x.x, x.y);
+    if (two) x1 = make_float2(x.z, x.w);
+  };
+  auto sv = [&](int line, int, int, int j, float2 v) {
+    const int w = j - (MID ? PN / 4 : a.out_c0);
+    if ((unsigned)w < (unsigned)(MID ? PN / 2 : a.Wout) && (line == 0 || two)) st_stream((line ? dst1 : dst0) + w, v);
+  };
+  fft_pow2_run2<true, PN, TT, FFT_ROWS>(lds, twl, tid, ld, sv, tw_hook);
+}
+
+// 4 waves / SIMD: 128 VGPRs for the two lines; at 8192 points two 8-wave workgroups per CU.  (The
+// 4096-point schedule 16 16 16 ends in a full radix-16 stage whose twiddles spill at 128: 3 there.)
+constexpr int pair_waves_per_eu(int n) { return n == 4096 ? 3 : 4; }
+template <int PN, bool MID>
+__global__ void __launch_bounds__(Geo<PN>::T) __attribute__((amdgpu_waves_per_eu(pair_waves_per_eu(PN))))
+asm_rows_inv_pair(const float2* __restrict__ U, float2* __restrict__ out, FftPlan pw, AsmArgs a) {
+  rows_inv_pair_body<PN, MID>(U, out, pw, a);
+}
+
 // ---------------------------------------------------------------------------------------------
 // z-x slice (thz_asm_slice_forward): one output row of every plane of a z-sweep
 // (experiment_extend_depth_of_focus.ipynb:229-263 keeps final_field.data[0, 0, 49, :] per z).
@@ -2113,7 +2174,9 @@ static int ensure_lds_attr() {
       if constexpr (rss_acc_compiled(PN))
         ks.insert(ks.end(), {(const void*)rsc_slice_acc<PN, 2>, (const void*)rsc_slice_acc<PN, 3>,
                              (const void*)rsc_slice_acc_adj<PN, 2>, (const void*)rsc_slice_acc_adj<PN, 3>});
-      if constexpr (PN == 8192) ks.push_back((const void*)asm_rows_inv_mid<PN>);
+      if constexpr (PN == 8192)
+        ks.insert(ks.end(), {(const void*)asm_rows_inv_mid<PN>, (const void*)asm_rows_inv_pair<PN, true>});
+      if constexpr (PN > 0) ks.push_back((const void*)asm_rows_inv_pair<PN, false>);
     };
     for_each_size(Pow2Sizes{}, planes);
     planes(Size<0>{});
@@ -2314,19 +2377,34 @@ static int launch_cols(const AsmPlan& p, AsmArgs& a, bool tables, const float2* 
   return THZ_OK;
 }
 
+// thz_asm_row_pairs: -1 the library's choice, 0 one row per workgroup, 1 row pairs wherever the
+// pair kernel exists (read per call, so a parity test can run both forms in one process)
+static std::atomic<int> g_row_pairs{-1};
+
+// K3 on row pairs?  By default where it was measured: the middle-half crop of P = 8192 (cfg2, K3 per
+// 64 planes: DESIGN.md §22); every plain power-of-two size when forced.
+static bool k3_pairs(int Pw, bool loss, bool mid) {
+  if (loss || !pow2_kind(Pw)) return false;
+  const int mode = g_row_pairs.load(std::memory_order_relaxed);
+  return mode < 0 ? mid && Pw == 8192 : mode > 0;
+}
+
 // K3 over the a.nz planes in U: plain, or with the loss sums (a.ls), each also with the crop as
-// constants (k3_mid)
+// constants (k3_mid); the plain power-of-two form also on row pairs (k3_pairs)
 static int launch_k3(const AsmPlan& p, const AsmArgs& a, const float2* U, void* out) {
   const int Pw = p.g.Pw;
-  const bool loss = a.ls.stats != nullptr, mid = k3_mid(Pw, a);
+  const bool loss = a.ls.stats != nullptr, mid = k3_mid(Pw, a), pairs = k3_pairs(Pw, loss, mid);
   PassKernel k = nullptr;
   if (mid && Pw == Mx300::N) k = loss ? asm_rows_inv_loss_mid<Mx300::N> : asm_rows_inv_mid<Mx300::N>;
+  else if (pairs && mid) k = asm_rows_inv_pair<8192, true>;
+  else if (pairs) on_pow2_only(Pw, [&](auto N) { k = asm_rows_inv_pair<N(), false>; });
   else if (mid && !loss) k = asm_rows_inv_mid<8192>;
   else if (loss) on_rows(Pw, [&](auto N) { k = asm_rows_inv_loss<N()>; });
   else on_rows(Pw, [&](auto N) { k = asm_rows_inv<N()>; });
   KernelTimer kt("asm_rows_inv", p.s);
-  hipLaunchKernelGGL(k, dim3(a.nz * a.BC * a.Hout), dim3(rows_threads(Pw)), fft_lds_bytes_io(Pw), p.s, U, (float2*)out,
-                     p.pw, a);
+  const int rows = pairs ? (a.Hout + 1) / 2 : a.Hout;  // workgroups per plane
+  hipLaunchKernelGGL(k, dim3(a.nz * a.BC * rows), dim3(rows_threads(Pw)), fft_lds_bytes_io(Pw, pairs ? 2 : 1), p.s, U,
+                     (float2*)out, p.pw, a);
   THZ_LAUNCH_CHECK();
   int e;
   if (loss && (e = launch_loss_finish(a.ls, p.s))) return e;
@@ -2533,6 +2611,12 @@ extern "C" int thz_asm_slice_adjoint(const thz_asm_desc* d, int row, const void*
   int e = asm_plan(d, Pipe::SliceAdjoint, row, grad_out && grad_in, workspace, workspace_bytes, stream, &p);
   if (e) return e;
   return run_slice_adjoint(p, row + p.a.in_r0, grad_out, grad_in);
+}
+
+extern "C" int thz_asm_row_pairs(int mode) {
+  if (mode < -1 || mode > 1) return fail(THZ_E_ARG, "thz_asm_row_pairs: mode %d (-1, 0 or 1)", mode);
+  g_row_pairs.store(mode, std::memory_order_relaxed);
+  return THZ_OK;
 }
 
 extern "C" int thz_asm_band(const thz_asm_desc* d, int* ncols, int* z_chunk) {

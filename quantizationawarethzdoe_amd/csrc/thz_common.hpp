@@ -55,10 +55,12 @@ inline int fft_threads(int n) {
 // data rows + the two-level twiddle table of the power-of-two kernels
 inline size_t fft_lds_bytes(int n) { return (size_t)(lds_floats2(n) + tw_lds_count(n)) * sizeof(float2); }
 // LDS of a row / column workgroup that runs fft_pow2_run: the split-exchange image (one float
-// per element) for the compile-time power-of-two sizes, the complex image for runtime plans
-inline size_t fft_lds_bytes_io(int n) {
+// per element) for the compile-time power-of-two sizes, the complex image for runtime plans.
+// lines = 2 (power-of-two sizes only): the two-line transform's two images and one set of tables
+// (fft_pow2_run2; 73232 B at n = 8192, so two workgroups share a CU's 160 KB).
+inline size_t fft_lds_bytes_io(int n, int lines = 1) {
   const bool pow2 = n >= 1024 && n <= 16384 && (n & (n - 1)) == 0;
-  if (pow2) return (size_t)(lds_split_f2(n) + tw_lds_count(n)) * sizeof(float2);
+  if (pow2) return (size_t)(lines * lds_split_f2(n) + tw_lds_count(n)) * sizeof(float2);
   return fft_lds_bytes(n);
 }
 

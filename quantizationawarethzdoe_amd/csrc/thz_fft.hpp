@@ -911,6 +911,132 @@ __device__ __forceinline__ void fft_pow2_run(float2* lds, const Tw& tw, int tid,
   fft_pow2_split_io<INV, N, T, MODE>(reinterpret_cast<float*>(lds), tw, tid, ld, sv, hook);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Two-line form of the split-exchange transform (MODE 0 schedules): every thread carries the
+// same butterflies of TWO independent transforms ("lines") in one instruction stream.  What
+// depends on the thread index only -- twiddle reads and products, LDS addresses, barriers -- is
+// paid once per pair; each line's arithmetic is the one-line transform's (same helpers, same
+// order), so a line's results equal fft_pow2_split_io's bit for bit.  Line 1's exchange image
+// lies LS floats behind line 0's, a constant that folds into the DS offsets.
+//   in(m, r, idx, x0, x1): stage-0 operand idx of both lines
+//   sv(line, m, r, idx, v): last-stage result idx of one line
+// ---------------------------------------------------------------------------------------------
+template <int R, bool INV, int N, int L, int T, class Tw, class In>
+__device__ __forceinline__ void stage_core2(const Tw& tw, int tid, In& in, float2 (&v)[2][N / R / T][R]) {
+  constexpr int NB = N / R;
+  constexpr int MB = NB / T;
+  static_assert(MB * T == NB, "pow2 plan must tile exactly");
+  constexpr int TWS = N / (L * R);
+#pragma unroll
+  for (int m = 0; m < MB; ++m) {
+    const int i = tid + m * T;
+#pragma unroll
+    for (int r = 0; r < R; ++r) in(m, r, i + r * NB, v[0][m][r], v[1][m][r]);
+    if constexpr (L > 1) {
+      if constexpr (L * R == 256 && std::is_same<Tw, TwLds>::value) {
+        static_assert(L == 16, "the L R = 256 stage of a radix-16 schedule");
+        const int k = i & (L - 1);
+#pragma unroll
+        for (int r = 1; r < R; ++r) {
+          const float2 w = tw.t256[16 * r + k];
+          v[0][m][r] = cmul_tw<INV>(v[0][m][r], w);
+          v[1][m][r] = cmul_tw<INV>(v[1][m][r], w);
+        }
+      } else {
+        float2 w[R];
+        twiddle_powers<R>(tw, (i & (L - 1)) * TWS, w);
+#pragma unroll
+        for (int r = 1; r < R; ++r) {
+          v[0][m][r] = cmul_tw<INV>(v[0][m][r], w[r]);
+          v[1][m][r] = cmul_tw<INV>(v[1][m][r], w[r]);
+        }
+      }
+    }
+    dftR<R, INV>(v[0][m]);
+    dftR<R, INV>(v[1][m]);
+  }
+}
+
+template <bool INV, int N, int T, int MODE, int LS, int S = 0, int L = 1, class Tw, class In, class Sv,
+          class Hook = NoHook>
+__device__ __forceinline__ void fft_pow2_split2_io(float* lds, const Tw& tw, int tid, In& in, Sv& sv,
+                                                   Hook hook = Hook{}) {
+  using P = Pow2Sched<N>;
+  constexpr int R = P::radix(S, MODE);
+  static_assert(R <= 16, "two-line form: no lane-pair stage");
+  static_assert(LS >= 2 * lds_split_f2(N), "line 1's image starts behind line 0's");
+  constexpr int MB = N / R / T;
+  float2 v[2][MB][R];
+  stage_core2<R, INV, N, L, T>(tw, tid, in, v);
+  if constexpr (S == 0) hook();
+  if constexpr (S == P::nst(MODE) - 1) {
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      const int i = tid + m * T;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        sv(0, m, r, i + r * L, v[0][m][r]);  // last stage: L R = N, k = i
+        sv(1, m, r, i + r * L, v[1][m][r]);
+      }
+    }
+  } else {
+    constexpr int R2 = P::radix(S + 1, MODE);
+    static_assert(R2 <= 16, "two-line form: no lane-pair stage");
+    constexpr int NB2 = N / R2;
+    constexpr int MB2 = NB2 / T;
+    static_assert(split_lay<L>(N - 1) < 2 * lds_split_f2(N), "split layout exceeds the LDS image");
+    float2 nx[2][MB2][R2];
+    // as fft_pow2_split_io's exchange, both lines under one pair of barriers
+#pragma unroll
+    for (int part = 0; part < 2; ++part) {
+      __syncthreads();  // previous readers of the images are done
+#pragma unroll
+      for (int m = 0; m < MB; ++m) {
+        const int i = tid + m * T;
+        const int k = i & (L - 1);
+        const int i0 = m * T, k0 = i0 & (L - 1), j0 = (i0 - k0) * R + k0;  // folds after unrolling
+        float* dst = lds + split_lay<L>((i - k) * R + k);
+#pragma unroll
+        for (int line = 0; line < 2; ++line)
+#pragma unroll
+          for (int r = 0; r < R; ++r)
+            dst[line * LS + split_lay<L>(j0 + r * L) - split_lay<L>(j0)] = part ? v[line][m][r].y : v[line][m][r].x;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int m = 0; m < MB2; ++m) {
+        const float* src = lds + split_lay<L>(tid + m * T);
+#pragma unroll
+        for (int line = 0; line < 2; ++line)
+#pragma unroll
+          for (int r = 0; r < R2; ++r) {
+            const float x = src[line * LS + split_lay<L>(m * T + r * NB2) - split_lay<L>(m * T)];
+            if (part) nx[line][m][r].y = x;
+            else nx[line][m][r].x = x;
+          }
+      }
+    }
+    auto in2 = [&](int m, int r, int, float2& x0, float2& x1) {
+      x0 = nx[0][m][r];
+      x1 = nx[1][m][r];
+    };
+    fft_pow2_split2_io<INV, N, T, MODE, LS, S + 1, L * R>(lds, tw, tid, in2, sv);
+  }
+}
+// float offset of line 1's image, and where the pair's (single) set of twiddle tables starts
+template <int N>
+__host__ __device__ constexpr int pair_line_floats() {
+  return 2 * lds_split_f2(N);
+}
+template <int N>
+__device__ __forceinline__ float2* tw_slot2(float2* lds) {
+  return lds + 2 * lds_split_f2(N);
+}
+template <bool INV, int N, int T, int MODE, class Tw, class Ld, class Sv, class Hook = NoHook>
+__device__ __forceinline__ void fft_pow2_run2(float2* lds, const Tw& tw, int tid, Ld& ld, Sv& sv, Hook hook = Hook{}) {
+  fft_pow2_split2_io<INV, N, T, MODE, pair_line_floats<N>()>(reinterpret_cast<float*>(lds), tw, tid, ld, sv, hook);
+}
+
 // Whole transform with the data in LDS (natural order in and out).
 template <bool INV, int N, int T, class Tw>
 __device__ __forceinline__ void fft_pow2(float2* lds, const Tw& tw, int tid) {
