@@ -23,14 +23,8 @@ import torch.nn as nn
 
 from quantizationawarethzdoe_amd.DataType.ElectricField import ElectricField
 from quantizationawarethzdoe_amd import propagation as _prop
-
-
-def _z_host(z):
-    if torch.is_tensor(z):
-        return [float(v) for v in z.detach().reshape(-1).cpu().tolist()]
-    if isinstance(z, (list, tuple, np.ndarray)):
-        return [float(v) for v in np.asarray(z).reshape(-1)]
-    return [float(z)]
+from quantizationawarethzdoe_amd.Props import _zx
+from quantizationawarethzdoe_amd.Props._zx import _z_host
 
 
 class _PendingAsm:
@@ -337,10 +331,7 @@ class ASM_prop(nn.Module):
         ``axis="y"`` transposes outside the slice (torch differentiates the transpose).  Inputs the
         slice kernels do not serve fall back to the full planes as above.  Any other value is a
         ValueError."""
-        if axis not in ("x", "y"):
-            raise ValueError(f"propagate_zx: axis must be 'x' or 'y', got {axis!r}")
-        if grad not in ("planes", "slice"):
-            raise ValueError(f"propagate_zx: grad must be 'planes' or 'slice', got {grad!r}")
+        _zx.check_axis_grad(axis, grad)
         zs = _z_host(z_list)
         pend = field._take_pending()
         data = pend.field if pend is not None else field.data
@@ -349,13 +340,7 @@ class ASM_prop(nn.Module):
         Ph, Pw = H + 2 * ph, W + 2 * pw
         unpad = (not self.do_padding) or self.do_unpad_after_pad
         Ho, Wo = (H, W) if unpad else (Ph, Pw)
-        n = Ho if axis == "x" else Wo
-        if row is None:
-            row = n // 2
-        row = int(row)
-        if not 0 <= row < n:
-            raise ValueError(f"propagate_zx: row {row} outside the valid range [0, {n}) of the output "
-                             f"{'rows' if axis == 'x' else 'columns'}")
+        row = _zx.output_row(row, Ho if axis == "x" else Wo, axis)
         bl = self._bandlimit_code()
         x = _prop.kernel_dtype(data, "ASM_prop", field.wavelengths)
         native = x.dtype == torch.complex64 and x.is_cuda
@@ -365,35 +350,18 @@ class ASM_prop(nn.Module):
             native = native and _prop.asm_slice_native(Ph)
         else:
             native = native and _prop.asm_slice_native(Pw) and (Ph == Pw or bl == 0)
-        max_z = _prop._lib.THZ_MAX_Z
         if not native:
-            # full planes, at most 10 GiB of them at a time (the library's own cap on its per-chunk
-            # intermediate), sliced per chunk
-            per_z = B * C * Ho * Wo * (16 if x.dtype == torch.complex128 else 8)
-            step = int(max(1, min(max_z, (10240 * 1024 * 1024) // per_z)))
-            outs = []
-            for k in range(0, len(zs), step):
-                planes = self._run(field, zs[k:k + step])
-                outs.append(planes[..., row, :] if axis == "x" else planes[..., :, row])
-            return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+            return _zx.sliced_planes(lambda chunk: self._run(field, chunk), zs,
+                                     B * C * Ho * Wo * (16 if x.dtype == torch.complex128 else 8), row, axis)
         self.shape = torch.Size([B, C, Ph, Pw])
         wl, sp = field.wavelengths_host, field.spacing_host
         self._zc_diagnostic(Ph, sp[0], wl, zs[0])
         try:
-            if grad == "slice":
-                if pend is not None:  # the differentiable modulate kernel; the slice reads its output
-                    x = _prop.kernel_dtype(pend.run(), "ASM_prop", field.wavelengths)
-                if axis == "y":
-                    x, sp, ph, pw = x.transpose(-1, -2), (sp[1], sp[0]), pw, ph
-                return _prop.asm_propagate_zx(x, wl, sp, zs, row, ph, pw, unpad=unpad, bandlimit=bl)
+            if pend is not None:  # grad="slice": the differentiable modulate kernel; the slice reads its output
+                x = _prop.kernel_dtype(pend.run(), "ASM_prop", field.wavelengths)
             if axis == "y":
-                x, sp, ph, pw = x.detach().transpose(-1, -2).contiguous(), (sp[1], sp[0]), pw, ph
-            else:
-                x = x.detach()
-            out = torch.empty((len(zs), B, C, Wo if axis == "x" else Ho), dtype=torch.complex64, device=x.device)
-            for k in range(0, len(zs), max_z):
-                _prop.asm_slice_apply(x, wl, sp, zs[k:k + max_z], row, ph, pw, unpad, bl, out=out[k:k + max_z])
+                x, sp, ph, pw = x.transpose(-1, -2), (sp[1], sp[0]), pw, ph
+            return _zx.native_sweep("asm", x, wl, sp, zs, row, (ph, pw, unpad, bl))
         except RuntimeError as err:
             self._oom_hint()
             raise err
-        return out

@@ -17,24 +17,12 @@ import torch.nn as nn
 
 from quantizationawarethzdoe_amd.DataType.ElectricField import ElectricField
 from quantizationawarethzdoe_amd import propagation as _prop
-
-
-def _f(v):
-    return float(v.detach().cpu()) if torch.is_tensor(v) else float(v)
+from quantizationawarethzdoe_amd.Props import _zx
+from quantizationawarethzdoe_amd.Props._zx import _f, _z_host
 
 
 def _pow2(n):
     return n > 0 and n & (n - 1) == 0
-
-
-def _z_host(z):
-    """The plane distances of a z-sweep as host floats (a tensor, a sequence or one value)."""
-    if torch.is_tensor(z):
-        return [float(v) for v in z.detach().reshape(-1).cpu().tolist()]
-    try:
-        return [_f(v) for v in z]
-    except TypeError:
-        return [float(z)]
 
 
 class CZT_prop(nn.Module):
@@ -171,51 +159,29 @@ class CZT_prop(nn.Module):
         mirrors the collapse, nothing of a plane's size per z in either direction); ``axis="y"``
         transposes outside the slice (torch differentiates the transpose).  The other inputs listed
         above still take the full planes.  Any other value is a ValueError."""
-        if axis not in ("x", "y"):
-            raise ValueError(f"propagate_zx: axis must be 'x' or 'y', got {axis!r}")
-        if grad not in ("planes", "slice"):
-            raise ValueError(f"propagate_zx: grad must be 'planes' or 'slice', got {grad!r}")
+        _zx.check_axis_grad(axis, grad)
         outH, outW, odx, ody = self._out_grid(field, outputHeight, outputWidth, outputPixel_dx, outputPixel_dy)
-        n = outW if axis == "x" else outH
-        if row is None:
-            row = n // 2
-        row = int(row)
-        if not 0 <= row < n:
-            raise ValueError(f"propagate_zx: row {row} outside the valid range [0, {n}) of the output "
-                             f"{'rows' if axis == 'x' else 'columns'}")
+        row = _zx.output_row(row, outW if axis == "x" else outH, axis)
         zs = _z_host(z_list)
         sp = tuple(field.spacing_host)
         x = _prop.kernel_dtype(field.data, "CZT_prop", field.wavelengths)
         B, C, H, W = x.shape
-        max_z = _prop._lib.THZ_MAX_Z
         diff = torch.is_grad_enabled() and x.requires_grad
         native = (x.dtype == torch.complex64 and x.is_cuda and not (diff and grad == "planes")
                   and not self._empty_plane(H, W, outH, outW) and (axis == "x" or sp[0] == sp[1]))
         if native:
-            wl = tuple(field.wavelengths_host)
             if axis == "y":
-                xs, geo = x.transpose(-1, -2), ((sp[1], sp[0]), outW, outH, ody, odx)
+                xs, sps, geo = x.transpose(-1, -2), (sp[1], sp[0]), (outW, outH, ody, odx)
             else:
-                xs, geo = x, (sp, outH, outW, odx, ody)
+                xs, sps, geo = x, sp, (outH, outW, odx, ody)
             try:
-                if diff:  # grad="slice": the slice kernels forward, thz_czt_slice_adjoint backward
-                    return _prop.czt_propagate_zx(xs, wl, geo[0], zs, row, geo[1], geo[2], geo[3], geo[4])
-                xs = xs.detach().contiguous()
-                out = torch.empty((len(zs), B, C, geo[1]), dtype=torch.complex64, device=x.device)
-                for k in range(0, len(zs), max_z):
-                    _prop.czt_slice_apply(xs, wl, geo[0], zs[k:k + max_z], row, geo[1], geo[2], geo[3], geo[4],
-                                          out=out[k:k + max_z])
-                return out
+                return _zx.native_sweep("czt", xs, tuple(field.wavelengths_host), sps, zs, row, geo)
             except _prop._lib.ThzError as err:  # validated before any launch: nothing ran
                 if err.code != _prop._lib.THZ_E_UNSUPPORTED:
                     raise
-        per_z = max(1, B * C * outW * outH * (16 if x.dtype == torch.complex128 else 8))
-        step = int(max(1, min(max_z, (10240 * 1024 * 1024) // per_z)))
-        outs = []
-        for k in range(0, len(zs), step):
-            planes = torch.stack([self._plane(x, field, zh, outH, outW, odx, ody) for zh in zs[k:k + step]])
-            outs.append(planes[..., row, :] if axis == "x" else planes[..., :, row])
-        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+        return _zx.sliced_planes(
+            lambda chunk: torch.stack([self._plane(x, field, zh, outH, outW, odx, ody) for zh in chunk]), zs,
+            B * C * outW * outH * (16 if x.dtype == torch.complex128 else 8), row, axis)
 
 
 class _CztFunction(torch.autograd.Function):

@@ -12,6 +12,7 @@ import contextlib
 import ctypes
 import math
 import threading
+import typing
 
 import torch
 
@@ -148,75 +149,6 @@ def asm_slice_native(padded_height):
     """True when the z-x slice kernels serve this padded height (the compile-time power-of-two
     column passes); other heights slice the full planes (ASM_prop.propagate_zx)."""
     return int(padded_height) in ASM_SLICE_HEIGHTS
-
-
-def asm_slice_apply(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, out=None):
-    """Raw launch of the z-x slice (thz_asm_slice_forward): data [B,C,H,W] complex64 -> [Z,B,C,Wo],
-    output row ``row`` of every plane of ``zs`` (at most THZ_MAX_Z), equal to
-    asm_apply(...)[:, :, :, row, :] without forming the planes.  Forward only; asm_propagate_zx is the
-    differentiable form (backward: asm_slice_adjoint)."""
-    _require_device(data, "ASM slice")
-    if data.dtype != torch.complex64:
-        raise TypeError(f"ASM slice kernels compute in complex64; got {data.dtype}")
-    L = _lib.lib()
-    data = data.contiguous()
-    B, C, H, W = data.shape
-    Wo = W if unpad else W + 2 * pad_w
-    d = _asm_desc(B, C, H, W, pad_h, pad_w, unpad, bandlimit, wavelengths, spacing, zs, False)
-    if out is None:
-        out = torch.empty((len(zs), B, C, Wo), dtype=torch.complex64, device=data.device)
-    elif tuple(out.shape) != (len(zs), B, C, Wo) or out.dtype != torch.complex64 or not out.is_contiguous():
-        raise ValueError(f"ASM slice: out must be a contiguous complex64 {(len(zs), B, C, Wo)} tensor")
-    _launch(L.thz_asm_slice_workspace_size, L.thz_asm_slice_forward, d, data.device, int(row), data, out)
-    return out
-
-
-def asm_slice_adjoint(g, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, height):
-    """Raw launch of the z-x slice's adjoint (thz_asm_slice_adjoint): the cotangent g [Z,B,C,Wo]
-    complex64 of asm_slice_apply(x [B,C,height,W], ..., row, ...) -> [B,C,height,W], the sum over the
-    planes of each plane's adjoint -- asm_apply(g placed at row ``row`` of zero planes, adjoint=True)
-    without forming the planes.  ``height`` is the field's H (g does not carry it).  At most
-    THZ_MAX_Z planes."""
-    _require_device(g, "ASM slice adjoint")
-    if g.dtype != torch.complex64:
-        raise TypeError(f"ASM slice kernels compute in complex64; got {g.dtype}")
-    L = _lib.lib()
-    g = g.contiguous()
-    Z, B, C, Wo = g.shape
-    if Z != len(zs):
-        raise ValueError(f"ASM slice adjoint: {Z} gradient rows for {len(zs)} z values")
-    H, W = int(height), Wo - (0 if unpad else 2 * pad_w)
-    d = _asm_desc(B, C, H, W, pad_h, pad_w, unpad, bandlimit, wavelengths, spacing, zs, True)
-    gin = torch.empty((B, C, H, W), dtype=torch.complex64, device=g.device)
-    _launch(L.thz_asm_slice_adjoint_workspace_size, L.thz_asm_slice_adjoint, d, g.device, int(row), g, gin)
-    return gin
-
-
-class _AsmSliceFunction(torch.autograd.Function):
-    """The z-x slice with its native backward: forward asm_slice_apply, backward asm_slice_adjoint.
-    A linear map: nothing is saved but the configuration."""
-
-    @staticmethod
-    def forward(ctx, data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit):
-        ctx.cfg = (wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, data.shape[-2])
-        return asm_slice_apply(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit)
-
-    @staticmethod
-    def backward(ctx, g):
-        wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, height = ctx.cfg
-        gin = asm_slice_adjoint(g, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, height)
-        return gin, None, None, None, None, None, None, None, None
-
-
-def asm_propagate_zx(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad=True, bandlimit="exact"):
-    """Differentiable z-x slice on the slice kernels, forward and backward: [B,C,H,W] complex64 ->
-    [Z,B,C,Wo], output row ``row`` of every plane of ``zs`` (any length: chunks of THZ_MAX_Z planes).
-    The padded height must be one the slice kernels serve (asm_slice_native)."""
-    bl = _bandlimit(bandlimit)
-    wl, sp, zs = list(map(float, wavelengths)), tuple(map(float, spacing)), list(map(float, zs))
-    outs = [_AsmSliceFunction.apply(data, wl, sp, zs[k:k + _lib.THZ_MAX_Z], int(row), int(pad_h), int(pad_w),
-                                    bool(unpad), bl) for k in range(0, len(zs), _lib.THZ_MAX_Z)]
-    return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
 def _asm64_apply(data, wavelengths, spacing, zs, pad_h, pad_w, unpad, bandlimit, adjoint=False, out=None):
@@ -582,77 +514,6 @@ def _czt_slice_desc(B, C, H, W, outH, outW, spacing, odx, ody, wavelengths, zs, 
     return d
 
 
-def czt_slice_apply(data, wavelengths, spacing, zs, row, outH, outW, odx, ody, out=None):
-    """Raw launch of the CZT z-x slice (thz_czt_slice_forward): data [B,C,H,W] complex64 -> [Z,B,C,outH],
-    output row ``row`` (the p of out[b, c, p, q]) of every plane of ``zs`` (at most THZ_MAX_Z), equal to
-    czt_apply(..., z, ...)[:, :, row, :] per z without forming the planes.  Forward only;
-    czt_propagate_zx is the differentiable form (backward: czt_slice_adjoint)."""
-    _require_device(data, "CZT slice")
-    if data.dtype != torch.complex64:
-        raise TypeError(f"CZT slice kernels compute in complex64; got {data.dtype}")
-    L = _lib.lib()
-    data = data.contiguous()
-    B, C, H, W = data.shape
-    d = _czt_slice_desc(B, C, H, W, outH, outW, spacing, odx, ody, wavelengths, zs, row)
-    shape = (len(zs), B, C, int(outH))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.complex64, device=data.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.complex64 or not out.is_contiguous():
-        raise ValueError(f"CZT slice: out must be a contiguous complex64 {shape} tensor")
-    _launch(L.thz_czt_slice_workspace_size, L.thz_czt_slice_forward, d, data.device, data, out)
-    return out
-
-
-def czt_slice_adjoint(g, wavelengths, spacing, zs, row, outH, outW, odx, ody, field_hw, out=None):
-    """Raw launch of the CZT z-x slice's adjoint (thz_czt_slice_adjoint): the cotangent g [Z,B,C,outH]
-    complex64 of czt_slice_apply(x [B,C,H,W], ...) with (H, W) = field_hw -> [B,C,H,W], the sum over
-    the planes of each plane's adjoint -- czt_apply(g placed at row ``row`` of a zero plane,
-    adjoint=True) per z, summed, without forming a plane.  At most THZ_MAX_Z planes.  ``out``, when
-    given, is a contiguous complex64 [B,C,H,W] tensor; every element of it is overwritten."""
-    _require_device(g, "CZT slice adjoint")
-    if g.dtype != torch.complex64:
-        raise TypeError(f"CZT slice kernels compute in complex64; got {g.dtype}")
-    L = _lib.lib()
-    g = g.contiguous()
-    Z, B, C, n = g.shape
-    if Z != len(zs) or n != int(outH):
-        raise ValueError(f"CZT slice adjoint: gradient {tuple(g.shape)} is not [{len(zs)}, B, C, {int(outH)}]")
-    H, W = (int(v) for v in field_hw)
-    d = _czt_slice_desc(B, C, H, W, outH, outW, spacing, odx, ody, wavelengths, zs, row)
-    shape = (B, C, H, W)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.complex64, device=g.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.complex64 or not out.is_contiguous():
-        raise ValueError(f"CZT slice adjoint: out must be a contiguous complex64 {shape} tensor")
-    _launch(L.thz_czt_slice_adjoint_workspace_size, L.thz_czt_slice_adjoint, d, g.device, g, out)
-    return out
-
-
-class _CztSliceFunction(torch.autograd.Function):
-    """The CZT z-x slice with its native backward: forward czt_slice_apply, backward
-    czt_slice_adjoint.  A linear map: nothing is saved but the configuration."""
-
-    @staticmethod
-    def forward(ctx, data, wavelengths, spacing, zs, row, outH, outW, odx, ody):
-        ctx.cfg = (wavelengths, spacing, zs, row, outH, outW, odx, ody, tuple(data.shape[-2:]))
-        return czt_slice_apply(data, wavelengths, spacing, zs, row, outH, outW, odx, ody)
-
-    @staticmethod
-    def backward(ctx, g):
-        wavelengths, spacing, zs, row, outH, outW, odx, ody, hw = ctx.cfg
-        gin = czt_slice_adjoint(g, wavelengths, spacing, zs, row, outH, outW, odx, ody, hw)
-        return gin, None, None, None, None, None, None, None, None
-
-
-def czt_propagate_zx(data, wavelengths, spacing, zs, row, outH, outW, odx, ody):
-    """Differentiable CZT z-x slice on the slice kernels, forward and backward: [B,C,H,W] complex64 ->
-    [Z,B,C,outH], output row ``row`` of every plane of ``zs`` (any length: chunks of THZ_MAX_Z planes)."""
-    wl, sp, zs = list(map(float, wavelengths)), tuple(map(float, spacing)), list(map(float, zs))
-    outs = [_CztSliceFunction.apply(data, wl, sp, zs[k:k + _lib.THZ_MAX_Z], int(row), int(outH), int(outW),
-                                    float(odx), float(ody)) for k in range(0, len(zs), _lib.THZ_MAX_Z)]
-    return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
-
-
 def rsc_apply(data, wavelengths, spacing, z, vectorial=False, adjoint=False, field_hw=None):
     """Rayleigh-Sommerfeld convolution (Props/RSC_Prop.py:170-321) on the HIP kernels.
 
@@ -697,28 +558,202 @@ def _rsc_slice_desc(B, C, H, W, vectorial, spacing, wavelengths, zs, row):
     return d
 
 
+# -- z-x slices: one output row of every plane of a z-sweep -------------------------------------
+# The ASM, CZT and RSC / VRS slice kernels differ; the glue above them does not.  A family says what
+# differs (_SliceFamily), and the launches, the autograd Function and the THZ_MAX_Z driver below
+# exist once.  ``geo`` is the family's geometry tuple, the trailing positional arguments of its
+# ``*_slice_apply``: ASM (pad_h, pad_w, unpad, bandlimit), CZT (outH, outW, odx, ody), RSC (vectorial,).
+
+class _SliceFamily(typing.NamedTuple):
+    label: str                # "ASM": the prefix of the error texts
+    entries: tuple            # library entry names: forward, its workspace size, adjoint, its workspace size
+    row_positional: bool      # the row is an argument of the entry points (ASM), else a descriptor field
+    desc: typing.Callable     # (field shape, geo, wavelengths, spacing, zs, row, adjoint) -> descriptor
+    out_shape: typing.Callable    # (Z, field shape, geo) -> the forward's output shape
+    field_shape: typing.Callable  # (cotangent, zs, geo, extra) -> (B, C, H, W), or ValueError
+    apply: typing.Callable    # the public raw forward (data, wavelengths, spacing, zs, row, geo, out=None)
+    adjoint: typing.Callable  # the public raw adjoint (g, wavelengths, spacing, zs, row, geo, field shape)
+    empty_window: bool = False    # an empty output is returned (adjoint: zero) without a launch
+
+
+def _slice_entries(tag):
+    return (f"thz_{tag}_slice_forward", f"thz_{tag}_slice_workspace_size",
+            f"thz_{tag}_slice_adjoint", f"thz_{tag}_slice_adjoint_workspace_size")
+
+
+def _asm_slice_field(g, zs, geo, height):
+    Z, B, C, Wo = g.shape
+    if Z != len(zs):
+        raise ValueError(f"ASM slice adjoint: {Z} gradient rows for {len(zs)} z values")
+    return B, C, int(height), Wo - (0 if geo[2] else 2 * geo[1])
+
+
+def _czt_slice_field(g, zs, geo, field_hw):
+    Z, B, C, n = g.shape
+    if Z != len(zs) or n != int(geo[0]):
+        raise ValueError(f"CZT slice adjoint: gradient {tuple(g.shape)} is not [{len(zs)}, B, C, {int(geo[0])}]")
+    H, W = (int(v) for v in field_hw)
+    return B, C, H, W
+
+
+def _rsc_slice_out(Z, shape, geo):
+    B, C, _, W = shape
+    return Z, 3 if geo[0] else B, C, 2 * (W // 2)
+
+
+def _rsc_slice_field(g, zs, geo, field_shape):
+    shape = tuple(int(v) for v in field_shape)
+    gshape = _rsc_slice_out(len(zs), shape, geo)
+    if tuple(g.shape) != gshape:
+        raise ValueError(f"RSC slice adjoint: gradient {tuple(g.shape)} is not {list(gshape)}")
+    return shape
+
+
+# ``apply`` / ``adjoint`` name the public functions in lambdas, so they are looked up in this module
+# when called: what serves a propagate_zx is what a caller of the public function would get.
+# A fourth slice is one more entry here and its three public wrappers below.
+_SLICE_FAMILIES = {
+    "asm": _SliceFamily(
+        "ASM", _slice_entries("asm"), True,
+        desc=lambda s, geo, wl, sp, zs, row, adj: _asm_desc(*s, *geo, wl, sp, zs, adj),
+        out_shape=lambda Z, s, geo: (Z, s[0], s[1], s[3] if geo[2] else s[3] + 2 * geo[1]),
+        field_shape=_asm_slice_field,
+        apply=lambda x, wl, sp, zs, row, geo, out=None: asm_slice_apply(x, wl, sp, zs, row, *geo, out=out),
+        adjoint=lambda g, wl, sp, zs, row, geo, s: asm_slice_adjoint(g, wl, sp, zs, row, *geo, s[2])),
+    "czt": _SliceFamily(
+        "CZT", _slice_entries("czt"), False,
+        desc=lambda s, geo, wl, sp, zs, row, adj: _czt_slice_desc(*s, geo[0], geo[1], sp, geo[2], geo[3], wl, zs, row),
+        out_shape=lambda Z, s, geo: (Z, s[0], s[1], int(geo[0])),
+        field_shape=_czt_slice_field,
+        apply=lambda x, wl, sp, zs, row, geo, out=None: czt_slice_apply(x, wl, sp, zs, row, *geo, out=out),
+        adjoint=lambda g, wl, sp, zs, row, geo, s: czt_slice_adjoint(g, wl, sp, zs, row, *geo, s[2:])),
+    "rsc": _SliceFamily(
+        "RSC", _slice_entries("rsc"), False,
+        desc=lambda s, geo, wl, sp, zs, row, adj: _rsc_slice_desc(*s, geo[0], sp, wl, zs, row),
+        out_shape=_rsc_slice_out,
+        field_shape=_rsc_slice_field,
+        apply=lambda x, wl, sp, zs, row, geo, out=None: rsc_slice_apply(x, wl, sp, zs, row, *geo, out=out),
+        adjoint=lambda g, wl, sp, zs, row, geo, s: rsc_slice_adjoint(g, wl, sp, zs, row, s, *geo),
+        empty_window=True),  # W = 1: the reference's [..., W:] window is empty
+}
+
+
+def _slice_launch(fam, adjoint, src, wavelengths, spacing, zs, row, geo, extra, out):
+    """The one raw launch of a slice family: forward src = the field [B,C,H,W] -> ``out_shape``;
+    adjoint src = the cotangent of that -> [B,C,H,W], the field shape recovered with ``extra``.
+    At most THZ_MAX_Z planes; ``out``, when given, is checked and every element of it overwritten."""
+    who = f"{fam.label} slice adjoint" if adjoint else f"{fam.label} slice"
+    _require_device(src, who)
+    if src.dtype != torch.complex64:
+        raise TypeError(f"{fam.label} slice kernels compute in complex64; got {src.dtype}")
+    L = _lib.lib()
+    src = src.contiguous()
+    field = fam.field_shape(src, zs, geo, extra) if adjoint else tuple(src.shape)
+    d = fam.desc(field, geo, wavelengths, spacing, zs, row, adjoint)
+    shape = tuple(field) if adjoint else tuple(fam.out_shape(len(zs), field, geo))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex64, device=src.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.complex64 or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous complex64 {shape} tensor")
+    if fam.empty_window and (src if adjoint else out).numel() == 0:
+        return out.zero_() if adjoint else out
+    run, size = (getattr(L, name) for name in fam.entries[2 * adjoint:2 * adjoint + 2])
+    _launch(size, run, d, src.device, *((int(row),) if fam.row_positional else ()), src, out)
+    return out
+
+
+class _SliceFunction(torch.autograd.Function):
+    """A z-x slice with its native backward: forward the family's ``*_slice_apply``, backward its
+    ``*_slice_adjoint``.  A linear map: nothing is saved but the family and the configuration."""
+
+    @staticmethod
+    def forward(ctx, data, fam, wavelengths, spacing, zs, row, geo):
+        ctx.cfg = (fam, wavelengths, spacing, zs, row, geo, tuple(data.shape))
+        return fam.apply(data, wavelengths, spacing, zs, row, geo)
+
+    @staticmethod
+    def backward(ctx, g):
+        fam, *cfg = ctx.cfg
+        return (fam.adjoint(g, *cfg),) + (None,) * 6
+
+
+def _slice_sweep(fam, data, wavelengths, spacing, zs, row, geo, diff):
+    """A z-sweep of any length on the slice kernels of ``fam``, in chunks of THZ_MAX_Z planes.
+    ``diff``: each chunk through _SliceFunction (backward: the family's adjoint), concatenated when
+    there is more than one; else the whole [Z, ...] result is allocated once and each chunk written
+    into its part of it (no copy, no second allocation; ``data`` enters detached)."""
+    wl, sp, zs = list(map(float, wavelengths)), tuple(map(float, spacing)), list(map(float, zs))
+    max_z = _lib.THZ_MAX_Z
+    if diff:
+        outs = [_SliceFunction.apply(data, fam, wl, sp, zs[k:k + max_z], row, geo) for k in range(0, len(zs), max_z)]
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+    data = data.detach().contiguous()
+    out = torch.empty(fam.out_shape(len(zs), tuple(data.shape), geo), dtype=torch.complex64, device=data.device)
+    for k in range(0, len(zs), max_z):
+        fam.apply(data, wl, sp, zs[k:k + max_z], row, geo, out[k:k + max_z])
+    return out
+
+
+def asm_slice_apply(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, out=None):
+    """Raw launch of the z-x slice (thz_asm_slice_forward): data [B,C,H,W] complex64 -> [Z,B,C,Wo],
+    output row ``row`` of every plane of ``zs`` (at most THZ_MAX_Z), equal to
+    asm_apply(...)[:, :, :, row, :] without forming the planes.  Forward only; asm_propagate_zx is the
+    differentiable form (backward: asm_slice_adjoint)."""
+    return _slice_launch(_SLICE_FAMILIES["asm"], False, data, wavelengths, spacing, zs, row,
+                         (pad_h, pad_w, unpad, bandlimit), None, out)
+
+
+def asm_slice_adjoint(g, wavelengths, spacing, zs, row, pad_h, pad_w, unpad, bandlimit, height):
+    """Raw launch of the z-x slice's adjoint (thz_asm_slice_adjoint): the cotangent g [Z,B,C,Wo]
+    complex64 of asm_slice_apply(x [B,C,height,W], ..., row, ...) -> [B,C,height,W], the sum over the
+    planes of each plane's adjoint -- asm_apply(g placed at row ``row`` of zero planes, adjoint=True)
+    without forming the planes.  ``height`` is the field's H (g does not carry it).  At most
+    THZ_MAX_Z planes."""
+    return _slice_launch(_SLICE_FAMILIES["asm"], True, g, wavelengths, spacing, zs, row,
+                         (pad_h, pad_w, unpad, bandlimit), height, None)
+
+
+def asm_propagate_zx(data, wavelengths, spacing, zs, row, pad_h, pad_w, unpad=True, bandlimit="exact"):
+    """Differentiable z-x slice on the slice kernels, forward and backward: [B,C,H,W] complex64 ->
+    [Z,B,C,Wo], output row ``row`` of every plane of ``zs`` (any length: chunks of THZ_MAX_Z planes).
+    The padded height must be one the slice kernels serve (asm_slice_native)."""
+    return _slice_sweep(_SLICE_FAMILIES["asm"], data, wavelengths, spacing, zs, int(row),
+                        (int(pad_h), int(pad_w), bool(unpad), _bandlimit(bandlimit)), True)
+
+
+def czt_slice_apply(data, wavelengths, spacing, zs, row, outH, outW, odx, ody, out=None):
+    """Raw launch of the CZT z-x slice (thz_czt_slice_forward): data [B,C,H,W] complex64 -> [Z,B,C,outH],
+    output row ``row`` (the p of out[b, c, p, q]) of every plane of ``zs`` (at most THZ_MAX_Z), equal to
+    czt_apply(..., z, ...)[:, :, row, :] per z without forming the planes.  Forward only;
+    czt_propagate_zx is the differentiable form (backward: czt_slice_adjoint)."""
+    return _slice_launch(_SLICE_FAMILIES["czt"], False, data, wavelengths, spacing, zs, row,
+                         (outH, outW, odx, ody), None, out)
+
+
+def czt_slice_adjoint(g, wavelengths, spacing, zs, row, outH, outW, odx, ody, field_hw, out=None):
+    """Raw launch of the CZT z-x slice's adjoint (thz_czt_slice_adjoint): the cotangent g [Z,B,C,outH]
+    complex64 of czt_slice_apply(x [B,C,H,W], ...) with (H, W) = field_hw -> [B,C,H,W], the sum over
+    the planes of each plane's adjoint -- czt_apply(g placed at row ``row`` of a zero plane,
+    adjoint=True) per z, summed, without forming a plane.  At most THZ_MAX_Z planes.  ``out``, when
+    given, is a contiguous complex64 [B,C,H,W] tensor; every element of it is overwritten."""
+    return _slice_launch(_SLICE_FAMILIES["czt"], True, g, wavelengths, spacing, zs, row,
+                         (outH, outW, odx, ody), field_hw, out)
+
+
+def czt_propagate_zx(data, wavelengths, spacing, zs, row, outH, outW, odx, ody):
+    """Differentiable CZT z-x slice on the slice kernels, forward and backward: [B,C,H,W] complex64 ->
+    [Z,B,C,outH], output row ``row`` of every plane of ``zs`` (any length: chunks of THZ_MAX_Z planes)."""
+    return _slice_sweep(_SLICE_FAMILIES["czt"], data, wavelengths, spacing, zs, int(row),
+                        (int(outH), int(outW), float(odx), float(ody)), True)
+
+
 def rsc_slice_apply(data, wavelengths, spacing, zs, row, vectorial=False, out=None):
     """Raw launch of the RSC / VRS z-x slice (thz_rsc_slice_forward): data [B,C,H,W] complex64 ->
     [Z,Bo,C,Pw-W], output row ``row`` of every plane of ``zs`` (at most THZ_MAX_Z), equal to
     rsc_apply(..., z, vectorial)[:, :, row, :] per z without forming the planes or the kernel's
     2-D spectrum.  Forward only; rsc_propagate_zx is the differentiable form (backward:
     rsc_slice_adjoint)."""
-    _require_device(data, "RSC slice")
-    if data.dtype != torch.complex64:
-        raise TypeError(f"RSC slice kernels compute in complex64; got {data.dtype}")
-    L = _lib.lib()
-    data = data.contiguous()
-    B, C, H, W = data.shape
-    d = _rsc_slice_desc(B, C, H, W, vectorial, spacing, wavelengths, zs, row)
-    shape = (len(zs), 3 if vectorial else B, C, 2 * (W // 2))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.complex64, device=data.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.complex64 or not out.is_contiguous():
-        raise ValueError(f"RSC slice: out must be a contiguous complex64 {shape} tensor")
-    if out.numel() == 0:  # W = 1: the reference's [..., W:] window is empty
-        return out
-    _launch(L.thz_rsc_slice_workspace_size, L.thz_rsc_slice_forward, d, data.device, data, out)
-    return out
+    return _slice_launch(_SLICE_FAMILIES["rsc"], False, data, wavelengths, spacing, zs, row, (vectorial,), None, out)
 
 
 def rsc_slice_adjoint(g, wavelengths, spacing, zs, row, field_shape, vectorial=False, out=None):
@@ -728,47 +763,12 @@ def rsc_slice_adjoint(g, wavelengths, spacing, zs, row, field_shape, vectorial=F
     of a zero plane, adjoint=True) per z, summed (VRS: with the Ez chain of each plane's own r), without
     forming a plane.  At most THZ_MAX_Z planes.  ``out``, when given, is a contiguous complex64
     [B,C,H,W] tensor; every element of it is overwritten."""
-    _require_device(g, "RSC slice adjoint")
-    if g.dtype != torch.complex64:
-        raise TypeError(f"RSC slice kernels compute in complex64; got {g.dtype}")
-    L = _lib.lib()
-    g = g.contiguous()
-    B, C, H, W = (int(v) for v in field_shape)
-    gshape = (len(zs), 3 if vectorial else B, C, 2 * (W // 2))
-    if tuple(g.shape) != gshape:
-        raise ValueError(f"RSC slice adjoint: gradient {tuple(g.shape)} is not {list(gshape)}")
-    d = _rsc_slice_desc(B, C, H, W, vectorial, spacing, wavelengths, zs, row)
-    shape = (B, C, H, W)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.complex64, device=g.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.complex64 or not out.is_contiguous():
-        raise ValueError(f"RSC slice adjoint: out must be a contiguous complex64 {shape} tensor")
-    if g.numel() == 0:  # W = 1: the forward's window is empty and its adjoint zero
-        return out.zero_()
-    _launch(L.thz_rsc_slice_adjoint_workspace_size, L.thz_rsc_slice_adjoint, d, g.device, g, out)
-    return out
-
-
-class _RscSliceFunction(torch.autograd.Function):
-    """The RSC / VRS z-x slice with its native backward: forward rsc_slice_apply, backward
-    rsc_slice_adjoint.  A linear map: nothing is saved but the configuration."""
-
-    @staticmethod
-    def forward(ctx, data, wavelengths, spacing, zs, row, vectorial):
-        ctx.cfg = (wavelengths, spacing, zs, row, vectorial, tuple(data.shape))
-        return rsc_slice_apply(data, wavelengths, spacing, zs, row, vectorial)
-
-    @staticmethod
-    def backward(ctx, g):
-        wavelengths, spacing, zs, row, vectorial, shape = ctx.cfg
-        return rsc_slice_adjoint(g, wavelengths, spacing, zs, row, shape, vectorial), None, None, None, None, None
+    return _slice_launch(_SLICE_FAMILIES["rsc"], True, g, wavelengths, spacing, zs, row, (vectorial,), field_shape,
+                         out)
 
 
 def rsc_propagate_zx(data, wavelengths, spacing, zs, row, vectorial=False):
     """Differentiable RSC / VRS z-x slice on the slice kernels, forward and backward: [B,C,H,W]
     complex64 -> [Z,Bo,C,2(W//2)], output row ``row`` of every plane of ``zs`` (any length: chunks of
     THZ_MAX_Z planes)."""
-    wl, sp, zs = list(map(float, wavelengths)), tuple(map(float, spacing)), list(map(float, zs))
-    outs = [_RscSliceFunction.apply(data, wl, sp, zs[k:k + _lib.THZ_MAX_Z], int(row), bool(vectorial))
-            for k in range(0, len(zs), _lib.THZ_MAX_Z)]
-    return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+    return _slice_sweep(_SLICE_FAMILIES["rsc"], data, wavelengths, spacing, zs, int(row), (bool(vectorial),), True)
