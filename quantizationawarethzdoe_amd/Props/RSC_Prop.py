@@ -8,7 +8,7 @@ ifft2(...)[..., H:, W:] (so an odd N returns N-1 samples, :207); VRS_prop forms 
 field's Ex/Ey planes and returns 3 planes.  One documented difference: where the reference's
 diagnostic crashes (z_min1 = 0 is an int without ``.detach``, :112-117) this mirror prints
 0.000 mm and continues.  The math runs in libthzdoe's gfx950 kernels (the spatial-kernel
-FFT and the convolution passes of thz_asm.hip).
+FFT and the convolution passes of thz_asm.hip; the z-x slice of thz_rsc.hip).
 """
 from __future__ import annotations
 

@@ -34,6 +34,7 @@
 
 #include "thz_common.hpp"
 #include "thz_dev.hpp"
+#include "thz_launch.hpp"
 #include "thz_wfft.hpp"
 
 
@@ -122,11 +123,6 @@ __global__ void czt_tables(CztArgs a, float2* __restrict__ ws, int pass) {
 __device__ __forceinline__ size_t vcol(int q, int h, int H) { return blk(q, h, H); }
 constexpr int VHS = CB;  // stride of consecutive h in a column of V
 
-template <int PN>
-struct CztGeo {
-  static constexpr int T = PN > 0 ? PN / pow2_v(PN) : 0;
-};
-
 // ---------------------------------------------------------------------------------------------
 // Pass A: rows (W axis).  in [BC][H][W] -> V [BC][q][h], q in [0, outH)
 // ---------------------------------------------------------------------------------------------
@@ -160,7 +156,7 @@ __global__ void __launch_bounds__(1024) czt_rows(const float2* __restrict__ in, 
   int tid = threadIdx.x;
   if constexpr (PN > 0) {
     using S = Pow2Sched<PN>;
-    constexpr int TT = CztGeo<PN>::T;
+    constexpr int TT = Geo<PN>::T;
     constexpr int RL = S::radix(S::NST - 1, false);
     constexpr int MBL = PN / RL / TT;
     float2 sp[MBL][RL];
@@ -218,7 +214,7 @@ __global__ void __launch_bounds__(1024) czt_cols(const float2* __restrict__ V, f
   int tid = threadIdx.x;
   if constexpr (PN > 0) {
     using S = Pow2Sched<PN>;
-    constexpr int TT = CztGeo<PN>::T;
+    constexpr int TT = Geo<PN>::T;
     constexpr int RL = S::radix(S::NST - 1, false);
     constexpr int MBL = PN / RL / TT;
     float2 sp[MBL][RL];
@@ -479,7 +475,7 @@ __device__ __forceinline__ void czt_adj_line(float2* lds, const FftPlan& pl, con
   int tid = threadIdx.x;
   if constexpr (PN > 0) {
     using S = Pow2Sched<PN>;
-    constexpr int TT = CztGeo<PN>::T;
+    constexpr int TT = Geo<PN>::T;
     constexpr int RL = S::radix(S::NST - 1, false);
     constexpr int MBL = PN / RL / TT;
     float2 sp[MBL][RL];
@@ -622,8 +618,6 @@ static int czt_validate(const thz_czt_desc* d) {
   return THZ_OK;
 }
 
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static void czt_layout(const thz_czt_desc* d, CztArgs* a, size_t* total) {
   a->BC = d->B * d->C;
   a->C = d->C;
@@ -666,54 +660,26 @@ static void czt_layout(const thz_czt_desc* d, CztArgs* a, size_t* total) {
     gend += (size_t)d->C * a->pb.nb * wf::N;
   }
   for (int c = 0; c < d->C; ++c) a->lam[c] = d->wavelengths[c];
-  const size_t tab = a256(gend * sizeof(float2));
-  const size_t vbytes = a256((size_t)a->BC * a->ncbA * CB * d->H * sizeof(float2));
+  const size_t tab = align256(gend * sizeof(float2));
+  const size_t vbytes = align256((size_t)a->BC * a->ncbA * CB * d->H * sizeof(float2));
   *total = tab + vbytes;
 }
 
-static int czt_pow2(int n) {
-  switch (n) {
-    case 1024: case 2048: case 4096: case 8192: case 16384: return n;
-    default: return 0;
-  }
-}
-
-#define THZ_CZT_SWITCH(n, KER, ...)                                                     \
-  switch (czt_pow2(n)) {                                                                 \
-    case 1024: hipLaunchKernelGGL(KER<1024>, __VA_ARGS__); break;                        \
-    case 2048: hipLaunchKernelGGL(KER<2048>, __VA_ARGS__); break;                        \
-    case 4096: hipLaunchKernelGGL(KER<4096>, __VA_ARGS__); break;                        \
-    case 8192: hipLaunchKernelGGL(KER<8192>, __VA_ARGS__); break;                        \
-    case 16384: hipLaunchKernelGGL(KER<16384>, __VA_ARGS__); break;                      \
-    default: hipLaunchKernelGGL(KER<0>, __VA_ARGS__); break;                             \
-  }
-
+// The large-LDS opt-in of the planes' passes, once: the overlap-add kernels and every np2 instantiation.
 static int czt_lds_attr() {
-  static std::once_flag once;
-  static hipError_t err = hipSuccess;
-  std::call_once(once, [] {
-    const int mx = (int)std::max(fft_lds_bytes(FFT_MAX_N), czb_cols_lds_bytes());
-    const void* ks[] = {
-        (const void*)czt_rows_blk<false>, (const void*)czt_rows_blk<true>,
-        (const void*)czt_cols_blk<false>, (const void*)czt_cols_blk<true>,
-        (const void*)czt_rows<0>,     (const void*)czt_rows<1024>, (const void*)czt_rows<2048>,
-        (const void*)czt_rows<4096>,  (const void*)czt_rows<8192>, (const void*)czt_rows<16384>,
-        (const void*)czt_cols<0>,     (const void*)czt_cols<1024>, (const void*)czt_cols<2048>,
-        (const void*)czt_cols<4096>,  (const void*)czt_cols<8192>, (const void*)czt_cols<16384>,
-        (const void*)czt_rows_adj<0>,  (const void*)czt_rows_adj<1024>, (const void*)czt_rows_adj<2048>,
-        (const void*)czt_rows_adj<4096>, (const void*)czt_rows_adj<8192>, (const void*)czt_rows_adj<16384>,
-        (const void*)czt_cols_adj<0>,  (const void*)czt_cols_adj<1024>, (const void*)czt_cols_adj<2048>,
-        (const void*)czt_cols_adj<4096>, (const void*)czt_cols_adj<8192>, (const void*)czt_cols_adj<16384>};
-    for (const void* k : ks) {
-      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-      if (e != hipSuccess) err = e;
-    }
-  });
-  if (err != hipSuccess) return fail(THZ_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(err));
-  return THZ_OK;
+  static const int rc = [] {
+    std::vector<const void*> ks{(const void*)czt_rows_blk<false>, (const void*)czt_rows_blk<true>,
+                                (const void*)czt_cols_blk<false>, (const void*)czt_cols_blk<true>};
+    auto passes = [&](auto N) {
+      ks.insert(ks.end(), {(const void*)czt_rows<N()>, (const void*)czt_cols<N()>, (const void*)czt_rows_adj<N()>,
+                           (const void*)czt_cols_adj<N()>});
+    };
+    for_each_size(Pow2Sizes{}, passes);
+    passes(Size<0>{});
+    return lds_opt_in(ks, std::max(fft_lds_bytes(FFT_MAX_N), czb_cols_lds_bytes()));
+  }();
+  return rc;
 }
-
-static int threads_pow2_or(int n) { return czt_pow2(n) ? n / pow2_v(n) : fft_threads(n); }
 
 // Per-device cache of a call's tables -- pre / post chirps and the filter spectra of both passes,
 // the workspace's leading table region -- keyed by everything they depend on (geometry, spacings,
@@ -744,7 +710,7 @@ static size_t czt_tab_bytes(const CztArgs& a, int C) {
   size_t gend = (size_t)a.tabStride * C;
   if (a.pa.nb) gend += (size_t)C * a.pa.nb * wf::N;
   if (a.pb.nb) gend += (size_t)C * a.pb.nb * wf::N;
-  return a256(gend * sizeof(float2));
+  return align256(gend * sizeof(float2));
 }
 
 // Build the tables of one call into tab (its workspace, or a cache buffer).
@@ -991,7 +957,7 @@ __global__ void __launch_bounds__(1024) czt_slice_line(const float2* __restrict_
   int tid = threadIdx.x;
   if constexpr (PN > 0) {
     using S = Pow2Sched<PN>;
-    constexpr int TT = CztGeo<PN>::T;
+    constexpr int TT = Geo<PN>::T;
     constexpr int RL = S::radix(S::NST - 1, false);
     constexpr int MBL = PN / RL / TT;
     float2 sp[MBL][RL];
@@ -1180,8 +1146,8 @@ static void czt_slice_layout(const thz_czt_slice_desc* d, CztSliceArgs* a, size_
   a->postB = take(1);
   a->tabStride = off;
   for (int c = 0; c < d->C; ++c) a->lam[c] = d->wavelengths[c];
-  *tab_bytes = a256((size_t)nzc * d->C * a->tabStride * sizeof(float2));
-  *total = *tab_bytes + a256((size_t)a->hs * nzc * a->BC * d->W * sizeof(float2));
+  *tab_bytes = align256((size_t)nzc * d->C * a->tabStride * sizeof(float2));
+  *total = *tab_bytes + align256((size_t)a->hs * nzc * a->BC * d->W * sizeof(float2));
 }
 
 // The adjoint's workspace: [the same tables][T [min(Z, CZS_ZC)][BC][W]] (H is not reduced: no splits)
@@ -1189,27 +1155,21 @@ static void czt_slice_adj_layout(const thz_czt_slice_desc* d, CztSliceArgs* a, s
   czt_slice_layout(d, a, tab_bytes, total);
   a->hs = 1;
   a->hlen = d->H;
-  *total = *tab_bytes + a256((size_t)a->nz * a->BC * d->W * sizeof(float2));
+  *total = *tab_bytes + align256((size_t)a->nz * a->BC * d->W * sizeof(float2));
 }
 
+// The large-LDS opt-in (lds_opt_in) of the slice's line transforms, once.
 static int czt_slice_lds_attr() {
-  static std::once_flag once;
-  static hipError_t err = hipSuccess;
-  std::call_once(once, [] {
-    const int mx = (int)fft_lds_bytes(FFT_MAX_N);
-    const void* ks[] = {(const void*)czt_slice_line<0>,    (const void*)czt_slice_line<1024>,
-                        (const void*)czt_slice_line<2048>, (const void*)czt_slice_line<4096>,
-                        (const void*)czt_slice_line<8192>, (const void*)czt_slice_line<16384>,
-                        (const void*)czt_slice_line_adj<0>,    (const void*)czt_slice_line_adj<1024>,
-                        (const void*)czt_slice_line_adj<2048>, (const void*)czt_slice_line_adj<4096>,
-                        (const void*)czt_slice_line_adj<8192>, (const void*)czt_slice_line_adj<16384>};
-    for (const void* k : ks) {
-      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-      if (e != hipSuccess) err = e;
-    }
-  });
-  if (err != hipSuccess) return fail(THZ_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(err));
-  return THZ_OK;
+  static const int rc = [] {
+    std::vector<const void*> ks;
+    auto lines = [&](auto N) {
+      ks.insert(ks.end(), {(const void*)czt_slice_line<N()>, (const void*)czt_slice_line_adj<N()>});
+    };
+    for_each_size(Pow2Sizes{}, lines);
+    lines(Size<0>{});
+    return lds_opt_in(ks, fft_lds_bytes(FFT_MAX_N));
+  }();
+  return rc;
 }
 
 }  // namespace thz
@@ -1233,8 +1193,7 @@ extern "C" int thz_czt_forward(const thz_czt_desc* d, const void* in, void* out,
   CztArgs a{};
   size_t need = 0;
   czt_layout(d, &a, &need);
-  if (!workspace || workspace_bytes < need)
-    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  if ((e = check_workspace(workspace, workspace_bytes, need))) return e;
   if ((e = czt_lds_attr())) return e;
   FftPlan plA, plB, pl1024;
   if ((e = get_plan(1024, &pl1024))) return e;
@@ -1242,16 +1201,20 @@ extern "C" int thz_czt_forward(const thz_czt_desc* d, const void* in, void* out,
   if ((e = get_plan(a.pa.np2, &plA))) return e;
   if ((e = get_plan(a.pb.np2, &plB))) return e;
   hipStream_t s = (hipStream_t)stream;
-  float2* V = (float2*)((char*)workspace + need - a256((size_t)a.BC * a.ncbA * CB * d->H * sizeof(float2)));
+  float2* V = (float2*)((char*)workspace + need - align256((size_t)a.BC * a.ncbA * CB * d->H * sizeof(float2)));
   const float2* ws = nullptr;  // the tables: cached, or built in the workspace's leading region
   if ((e = czt_tables_for(a, d, (float2*)workspace, s, &ws))) return e;
+  const int thA = threads_for(a.pa.np2), thB = threads_for(a.pb.np2);  // the np2 passes' workgroups and LDS
+  const size_t ldsA = fft_lds_bytes_io(a.pa.np2), ldsB = fft_lds_bytes_io(a.pb.np2);
   if (d->adjoint) {  // G [B, C, outW, outH] -> grad_in [B, C, H, W]: column pass first
     KernelTimer kt("czt_adjoint", s);
-    THZ_CZT_SWITCH(a.pb.np2, czt_cols_adj, dim3(a.BC * d->outH), dim3(threads_pow2_or(a.pb.np2)),
-                   fft_lds_bytes_io(a.pb.np2), s, (const float2*)in, V, ws, plB, a);
+    on_pow2(a.pb.np2, [&](auto N) {
+      hipLaunchKernelGGL(czt_cols_adj<N()>, dim3(a.BC * d->outH), dim3(thB), ldsB, s, (const float2*)in, V, ws, plB, a);
+    });
     THZ_LAUNCH_CHECK();
-    THZ_CZT_SWITCH(a.pa.np2, czt_rows_adj, dim3(a.BC * d->H), dim3(threads_pow2_or(a.pa.np2)),
-                   fft_lds_bytes_io(a.pa.np2), s, (const float2*)V, (float2*)out, ws, plA, a);
+    on_pow2(a.pa.np2, [&](auto N) {
+      hipLaunchKernelGGL(czt_rows_adj<N()>, dim3(a.BC * d->H), dim3(thA), ldsA, s, (const float2*)V, (float2*)out, ws, plA, a);
+    });
     THZ_LAUNCH_CHECK();
     kt.stop();
     return THZ_OK;
@@ -1262,8 +1225,9 @@ extern "C" int thz_czt_forward(const thz_czt_desc* d, const void* in, void* out,
       hipLaunchKernelGGL(d->W % CZB_BS ? czt_rows_blk<true> : czt_rows_blk<false>, dim3((a.BC * d->H + CZB_W - 1) / CZB_W), dim3(64 * CZB_W), czb_lds_bytes(CZB_W), s,
                          (const float2*)in, V, ws, a);
     } else {
-      THZ_CZT_SWITCH(a.pa.np2, czt_rows, dim3(a.BC * d->H), dim3(threads_pow2_or(a.pa.np2)),
-                     fft_lds_bytes_io(a.pa.np2), s, (const float2*)in, V, ws, plA, a);
+      on_pow2(a.pa.np2, [&](auto N) {
+        hipLaunchKernelGGL(czt_rows<N()>, dim3(a.BC * d->H), dim3(thA), ldsA, s, (const float2*)in, V, ws, plA, a);
+      });
     }
     THZ_LAUNCH_CHECK();
     kt.stop();
@@ -1276,8 +1240,9 @@ extern "C" int thz_czt_forward(const thz_czt_desc* d, const void* in, void* out,
       hipLaunchKernelGGL(d->H % CZB_BS ? czt_cols_blk<true> : czt_cols_blk<false>, dim3((a.BC * a.ncbA + 7) / 8 * 16), dim3(64 * CZB_WC), czb_cols_lds_bytes(),
                          s, (const float2*)V, (float2*)out, ws, a);
     } else {
-      THZ_CZT_SWITCH(a.pb.np2, czt_cols, dim3(a.BC * d->outH), dim3(threads_pow2_or(a.pb.np2)),
-                     fft_lds_bytes_io(a.pb.np2), s, (const float2*)V, (float2*)out, ws, plB, a);
+      on_pow2(a.pb.np2, [&](auto N) {
+        hipLaunchKernelGGL(czt_cols<N()>, dim3(a.BC * d->outH), dim3(thB), ldsB, s, (const float2*)V, (float2*)out, ws, plB, a);
+      });
     }
     THZ_LAUNCH_CHECK();
     kt.stop();
@@ -1303,8 +1268,7 @@ extern "C" int thz_czt_slice_forward(const thz_czt_slice_desc* d, const void* in
   CztSliceArgs a{};
   size_t tab = 0, need = 0;
   czt_slice_layout(d, &a, &tab, &need);
-  if (!workspace || workspace_bytes < need)
-    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  if ((e = check_workspace(workspace, workspace_bytes, need))) return e;
   const long wb = (d->W + CZS_THREADS - 1) / CZS_THREADS, ngmax = (a.nz + CZS_ZT - 1) / CZS_ZT;
   if (wb * ngmax * a.hs * a.BC > 0x7fffffffL || (long)CZS_ZC * a.BC > 0x7fffffffL)
     return fail(THZ_E_UNSUPPORTED, "CZT slice: B C = %d is too large for one launch", a.BC);
@@ -1336,9 +1300,11 @@ extern "C" int thz_czt_slice_forward(const thz_czt_slice_desc* d, const void* in
     }
     {
       KernelTimer kt("czt_slice_line", s);
-      THZ_CZT_SWITCH(a.pa.np2, czt_slice_line, dim3(a.nz * a.BC), dim3(threads_pow2_or(a.pa.np2)),
-                     fft_lds_bytes_io(a.pa.np2), s, (const float2*)P, (float2*)out + (size_t)k0 * a.BC * d->outH,
-                     (const float2*)ws, plA, a);
+      on_pow2(a.pa.np2, [&](auto N) {
+        hipLaunchKernelGGL(czt_slice_line<N()>, dim3(a.nz * a.BC), dim3(threads_for(a.pa.np2)),
+                           fft_lds_bytes_io(a.pa.np2), s, (const float2*)P,
+                           (float2*)out + (size_t)k0 * a.BC * d->outH, (const float2*)ws, plA, a);
+      });
       THZ_LAUNCH_CHECK();
       kt.stop();
     }
@@ -1364,8 +1330,7 @@ extern "C" int thz_czt_slice_adjoint(const thz_czt_slice_desc* d, const void* gr
   CztSliceArgs a{};
   size_t tab = 0, need = 0;
   czt_slice_adj_layout(d, &a, &tab, &need);
-  if (!workspace || workspace_bytes < need)
-    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  if ((e = check_workspace(workspace, workspace_bytes, need))) return e;
   const long wb = (d->W + CZS_THREADS - 1) / CZS_THREADS, nhb = (d->H + CZS_XR - 1) / CZS_XR;
   if (wb * nhb * a.BC > 0x7fffffffL || (long)CZS_ZC * a.BC > 0x7fffffffL)
     return fail(THZ_E_UNSUPPORTED, "CZT slice adjoint: B C = %d is too large for one launch", a.BC);
@@ -1388,9 +1353,11 @@ extern "C" int thz_czt_slice_adjoint(const thz_czt_slice_desc* d, const void* gr
     }
     {
       KernelTimer kt("czt_slice_line_adj", s);
-      THZ_CZT_SWITCH(a.pa.np2, czt_slice_line_adj, dim3(a.nz * a.BC), dim3(threads_pow2_or(a.pa.np2)),
-                     fft_lds_bytes_io(a.pa.np2), s, (const float2*)grad_out + (size_t)k0 * a.BC * d->outH, T,
-                     (const float2*)ws, plA, a);
+      on_pow2(a.pa.np2, [&](auto N) {
+        hipLaunchKernelGGL(czt_slice_line_adj<N()>, dim3(a.nz * a.BC), dim3(threads_for(a.pa.np2)),
+                           fft_lds_bytes_io(a.pa.np2), s, (const float2*)grad_out + (size_t)k0 * a.BC * d->outH, T,
+                           (const float2*)ws, plA, a);
+      });
       THZ_LAUNCH_CHECK();
       kt.stop();
     }

@@ -479,4 +479,12 @@ __device__ __forceinline__ void loss_store_part(LossAcc acc, const LossSink& ls,
 // loss_finish_kernel launch (thz_optics.hip): B workgroups
 int launch_loss_finish(const LossSink& ls, hipStream_t s);
 
+// VRS's Ez = Ex x / r + Ey y / r (Props/RSC_Prop.py:294-303) of the row passes of thz_asm.hip and thz_rsc.hip
+#pragma clang fp contract(off)
+__device__ __forceinline__ float2 vrs_ez(float2 ex, float2 ey, float x, float y, float z) {
+  const float r = sqrtf(x * x + y * y + z * z);
+  return make_float2((ex.x * x) / r + (ey.x * y) / r, (ex.y * x) / r + (ey.y * y) / r);
+}
+#pragma clang fp contract(on)
+
 }  // namespace thz

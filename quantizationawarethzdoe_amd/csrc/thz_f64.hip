@@ -18,6 +18,7 @@
 
 #include "thz_common.hpp"
 #include "thz_dev.hpp"
+#include "thz_launch.hpp"
 
 namespace thz {
 namespace f64 {
@@ -575,24 +576,14 @@ static int get_plan(int n, DPlan* out) {
   return THZ_OK;
 }
 
+// The large-LDS opt-in (lds_opt_in) of the fp64 kernels, once (they are not templated on size).
 static int lds_attr() {
-  static std::once_flag once;
-  static hipError_t err = hipSuccess;
-  std::call_once(once, [] {
-    const int mx = (int)lds_bytes(MAX_N);
-    const void* ks[] = {(const void*)fft_lines,    (const void*)conv_rows_fwd, (const void*)conv_cols,
-                        (const void*)conv_rows_inv, (const void*)czt_rows,     (const void*)czt_cols,
-                        (const void*)czt_rows_adj,  (const void*)czt_cols_adj};
-    for (const void* k : ks) {
-      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-      if (e != hipSuccess) err = e;
-    }
-  });
-  if (err != hipSuccess) return fail(THZ_E_HIP, "hipFuncSetAttribute(fp64): %s", hipGetErrorString(err));
-  return THZ_OK;
+  static const int rc = lds_opt_in({(const void*)fft_lines, (const void*)conv_rows_fwd, (const void*)conv_cols,
+                                    (const void*)conv_rows_inv, (const void*)czt_rows, (const void*)czt_cols,
+                                    (const void*)czt_rows_adj, (const void*)czt_cols_adj},
+                                   lds_bytes(MAX_N));
+  return rc;
 }
-
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static int lines(const double2* in, double2* out, int count, const DPlan& p, int inverse, size_t stride, int cstride,
                  hipStream_t s) {
@@ -613,9 +604,9 @@ static ConvGeom conv_geom(const ConvArgs& a, int Z) {
   ConvGeom g;
   const double per_z = (double)a.BC * a.Pw * a.Hout * sizeof(double2);
   g.zc = (int)std::max(1.0, std::min((double)Z, std::floor((8192.0 * 1024 * 1024) / per_z)));
-  g.t = a256((size_t)a.BC * a.Pw * a.Hin * sizeof(double2));
-  g.s = a256((size_t)a.BC * a.Pw * a.Ph * sizeof(double2));
-  g.u = a256((size_t)g.zc * a.BC * a.Pw * a.Hout * sizeof(double2));
+  g.t = align256((size_t)a.BC * a.Pw * a.Hin * sizeof(double2));
+  g.s = align256((size_t)a.BC * a.Pw * a.Ph * sizeof(double2));
+  g.u = align256((size_t)g.zc * a.BC * a.Pw * a.Hout * sizeof(double2));
   return g;
 }
 
@@ -726,7 +717,7 @@ static int rsc_args(const thz_rsc_desc64* d, RscPlan64* p) {
   a.nz = 1;
   a.zv[0] = d->z;
   for (int c = 0; c < d->C; ++c) a.lam[c] = d->wavelengths[c];
-  p->kt = a256((size_t)d->C * a.Ph * a.Pw * sizeof(double2));
+  p->kt = align256((size_t)d->C * a.Ph * a.Pw * sizeof(double2));
   p->kf = p->kt;
   return THZ_OK;
 }
@@ -796,7 +787,7 @@ static int czt_args(const thz_czt_desc64* d, CztArgs* a, size_t* total) {
     if (!(d->wavelengths[c] > 0.0)) return fail(THZ_E_ARG, "wavelength[%d] must be > 0", c);
     a->lam[c] = d->wavelengths[c];
   }
-  *total = a256(off * d->C * sizeof(double2)) + a256((size_t)a->BC * d->outH * d->H * sizeof(double2));
+  *total = align256(off * d->C * sizeof(double2)) + align256((size_t)a->BC * d->outH * d->H * sizeof(double2));
   return THZ_OK;
 }
 
@@ -831,8 +822,7 @@ extern "C" int thz_asm64_forward(const thz_asm_desc64* d, const void* in, void* 
   if (e) return e;
   if (!in || !out) return fail(THZ_E_ARG, "null data pointer");
   const f64::ConvGeom g = f64::conv_geom(a, d->Z);
-  if (!workspace || workspace_bytes < g.total())
-    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, g.total());
+  if ((e = check_workspace(workspace, workspace_bytes, g.total()))) return e;
   return f64::run_conv(a, d->Z, (const double2*)in, (double2*)out, (char*)workspace, (hipStream_t)stream);
 }
 
@@ -853,8 +843,7 @@ extern "C" int thz_rsc64_forward(const thz_rsc_desc64* d, const void* in, void* 
   if (e) return e;
   if (!in || !out) return fail(THZ_E_ARG, "null data pointer");
   const f64::ConvGeom g = f64::conv_geom(p.a, 1);
-  if (!workspace || workspace_bytes < p.kt + p.kf + g.total())
-    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, p.kt + p.kf + g.total());
+  if ((e = check_workspace(workspace, workspace_bytes, p.kt + p.kf + g.total()))) return e;
   if ((e = f64::lds_attr())) return e;
   hipStream_t s = (hipStream_t)stream;
   const int Ph = p.a.Ph, Pw = p.a.Pw;
@@ -901,15 +890,14 @@ extern "C" int thz_czt64_forward(const thz_czt_desc64* d, const void* in, void* 
   int e = f64::czt_args(d, &a, &need);
   if (e) return e;
   if (!in || !out) return fail(THZ_E_ARG, "null data pointer");
-  if (!workspace || workspace_bytes < need)
-    return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  if ((e = check_workspace(workspace, workspace_bytes, need))) return e;
   if ((e = f64::lds_attr())) return e;
   f64::DPlan pA, pB;
   if ((e = f64::get_plan(a.pa.np2, &pA))) return e;
   if ((e = f64::get_plan(a.pb.np2, &pB))) return e;
   hipStream_t s = (hipStream_t)stream;
   double2* ws = (double2*)workspace;
-  double2* V = (double2*)((char*)workspace + f64::a256(a.tabStride * d->C * sizeof(double2)));
+  double2* V = (double2*)((char*)workspace + align256(a.tabStride * d->C * sizeof(double2)));
   {
     KernelTimer kt("czt64_tables", s);
     const int nA = std::max({a.pa.m, a.pa.M, a.pa.np2}), nB = std::max({a.pb.m, a.pb.M, a.pb.np2});

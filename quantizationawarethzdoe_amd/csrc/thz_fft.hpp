@@ -34,6 +34,15 @@ constexpr int FFT_MAXV = 16;  // complex values held per thread per stage (N <= 
 // occupancy hides)
 __host__ __device__ constexpr int pow2_v(int) { return 16; }
 constexpr int pow2_log(int v) { return v <= 1 ? 0 : 1 + pow2_log(v >> 1); }
+// PN > 0: compile-time power-of-two transform with fused global I/O (blockDim == PN / FFT_MAXV):
+// the first Stockham stage reads its operands straight from global memory and the last
+// stage writes its results straight to global memory (coalesced in both cases), so a
+// transform costs NST-1 LDS round trips instead of NST+1.  PN == 0: runtime mixed-radix
+// plan, data staged through LDS.
+template <int PN>
+struct Geo {
+  static constexpr int T = PN > 0 ? PN / pow2_v(PN) : 0;
+};
 
 struct FftPlan {
   int n;                       // transform length

@@ -9,7 +9,7 @@ with HIP events around the whole map:
 then, in a pass of its own, the native path's per-kernel HIP-event times (thz_timing_*), the
 relative L2 between the two maps, and the slice kernels' register / scratch / occupancy lines from
 the compiler's resource summary (--resources FILE: lines collected beforehand with
-`hipcc -Rpass-analysis=kernel-resource-usage`; without it the script compiles csrc/thz_asm.hip for
+`hipcc -Rpass-analysis=kernel-resource-usage`; without it the script compiles csrc/thz_rsc.hip for
 the summary itself).  Plain text to --out.
 
     python scripts/rsc_zx_timing.py --out profiles/rsc_zx_timing.txt
@@ -32,7 +32,7 @@ def resource_lines(path=None):
         with open(path) as fh:
             text = fh.read()
     else:
-        src = os.path.join(ROOT, "quantizationawarethzdoe_amd", "csrc", "thz_asm.hip")
+        src = os.path.join(ROOT, "quantizationawarethzdoe_amd", "csrc", "thz_rsc.hip")
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         text = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize",
                                "-munsafe-fp-atomics", "-c", "-Rpass-analysis=kernel-resource-usage", src, "-o",

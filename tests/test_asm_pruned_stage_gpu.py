@@ -5,7 +5,7 @@ runs without them; a band that reaches P/4 runs the full stage.  The row pass (a
 only the loads of its zero operands and keeps the full stage (the pruned one measured slower there,
 DESIGN.md section 16); the same cases cover its load skip on both sides of the boundary.
 
-Geometry: P = 1024, the smallest instantiated power-of-two size (Pow2Sizes in csrc/thz_asm.hip; its
+Geometry: P = 1024, the smallest instantiated power-of-two size (Pow2Sizes in csrc/thz_launch.hpp; its
 inverse schedules are 16 x 16 x 4, radix 16 first, in both the column and the row pass).  Padding scale 1
 makes P = 2 N, so both passes reach that size only with a 512 x 512 field (a smaller field runs the
 runtime plans, which have no such stage).  White-noise inputs: the band edge carries energy.
