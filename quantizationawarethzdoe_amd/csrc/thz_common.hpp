@@ -58,7 +58,8 @@ inline int fft_threads(int n) {
 inline size_t fft_lds_bytes(int n) { return (size_t)(lds_floats2(n) + tw_lds_count(n)) * sizeof(float2); }
 // LDS of a row / column workgroup that runs fft_pow2_run: the split-exchange image (one float
 // per element) for the compile-time power-of-two sizes, the complex image for runtime plans.
-// lines = 2 (power-of-two sizes only): the two-line transform's two images and one set of tables
+// lines = 2 (power-of-two sizes only): the two-line transform's image (one float2 {line 0, line 1}
+// per element, the size of two one-line images) and one set of tables
 // (fft_pow2_run2; 73232 B at n = 8192, so two workgroups share a CU's 160 KB).
 inline size_t fft_lds_bytes_io(int n, int lines = 1) {
   const bool pow2 = n >= 1024 && n <= 16384 && (n & (n - 1)) == 0;
