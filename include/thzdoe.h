@@ -24,6 +24,7 @@
  *   thz_doe_*        Components/QuantizedDOE.py:44-126  DOELayer.modulate (+ backward)
  *   thz_quant_*      Components/QuantizedDOE.py:181-1388 quantized height maps (+ backward)
  *   thz_fft_*        utils/Helper_Functions.py:99-160 ft2/ift2 (centred ortho FFT)
+ *   thz_stokes_*, thz_polarization_ellipse*  Addons/Polarization.py:45-92  PolarizationAnalyser
  */
 #ifndef THZDOE_H_
 #define THZDOE_H_
@@ -59,7 +60,9 @@ typedef void* thz_stream_t; /* hipStream_t */
  * thz_czt_slice_workspace_size and thz_czt_slice_forward with their own new thz_czt_slice_desc, and
  * thz_czt_slice_adjoint_workspace_size and thz_czt_slice_adjoint on the same descriptor, and
  * thz_rsc_slice_workspace_size and thz_rsc_slice_forward with their new thz_rsc_slice_desc, and
- * thz_rsc_slice_adjoint_workspace_size and thz_rsc_slice_adjoint on the same descriptor):
+ * thz_rsc_slice_adjoint_workspace_size and thz_rsc_slice_adjoint on the same descriptor, and the
+ * descriptor-free polarization entries thz_stokes_forward, thz_stokes_backward,
+ * thz_polarization_ellipse, thz_stokes64_forward and thz_polarization_ellipse64):
  * a caller compares thz_abi_version()
  * with the THZ_ABI_VERSION it was compiled against before its first call, since a shorter
  * struct from an older header would make the library read past it.  Descriptors are plain C
@@ -573,6 +576,34 @@ int thz_resample_forward(const thz_resample_desc* d, const void* in, void* out, 
 int thz_resample_backward(const thz_resample_desc* d, const void* grad_out, void* grad_in, thz_stream_t stream);
 
 /*
+ * Polarization analysis of a vectorial field (Addons/Polarization.py:45-92,
+ * PolarizationAnalyser.polarization_state / polarization_ellipse), one streaming pass each.
+ * ex, ey: the Ex and Ey component planes, each n contiguous complex64 values (8-byte aligned; the
+ * planes of a [B >= 2, ...] tensor -- the Ez plane is never passed or read).  Outputs are four
+ * planes of n floats, [4][n] contiguous.  Null pointers and n < 0 are THZ_E_ARG; n == 0 is THZ_OK
+ * and launches nothing.  When every pointer is 16-byte aligned and n % 4 == 0 each lane moves its
+ * four pixels as 16-byte accesses; otherwise the same kernel body runs with element-width accesses
+ * (bit-identical results).
+ *
+ * thz_stokes_forward (:49-56): out = I, Q, U, V with
+ *   I = |Ex|^2 + |Ey|^2,  Q = |Ex|^2 - |Ey|^2,  U = 2 Re(Ex conj Ey),  V = 2 Im(Ex conj Ey).
+ * thz_stokes_backward: the cotangent of a real loss in torch's convention (dL/dRe + i dL/dIm),
+ * grad = gI, gQ, gU, gV [4][n]:
+ *   gEx = 2 [(gI + gQ) Ex + (gU + i gV) Ey],   gEy = 2 [(gI - gQ) Ey + (gU - i gV) Ex].
+ * thz_polarization_ellipse (:72-84): out = A, B, theta, h from the fields in one pass (the Stokes
+ * planes are not materialised), the reference's sequence in its order with eps = 1e-6:
+ *   Ip = sqrt(Q^2 + U^2 + V^2),  L = (Q + eps) + i U,
+ *   A = sqrt((Ip + |L| + eps) / 2),  B = sqrt((Ip - |L| + eps) / 2),
+ *   theta = atan2(U, Q + eps) / 2,  h = sign(V + eps).
+ * One deliberate deviation: for exactly linear polarization rounding can leave B's radicand
+ * slightly negative, where the reference returns NaN; the radicand is clamped at 0 here.
+ */
+int thz_stokes_forward(const void* ex, const void* ey, long long n, float* out, thz_stream_t stream);
+int thz_stokes_backward(const void* ex, const void* ey, long long n, const float* grad, void* gex, void* gey,
+                        thz_stream_t stream);
+int thz_polarization_ellipse(const void* ex, const void* ey, long long n, float* out, thz_stream_t stream);
+
+/*
  * Batched 1-D FFT along the contiguous axis (the building block of ft2/ift2,
  * utils/Helper_Functions.py:150, without shifts): in/out [rows, n], unnormalised,
  * inverse != 0 for the backward transform.  n <= 16384, any factorisation.
@@ -630,6 +661,11 @@ int thz_rsc64_forward(const thz_rsc_desc64* d, const void* in, void* out, void* 
 /* Batched 1-D FFT of complex128 rows (as thz_fft_rows), n <= 8192. */
 int thz_fft64_rows(const void* in, void* out, int rows, int n, int inverse, thz_stream_t stream);
 
+/* thz_stokes_forward / thz_polarization_ellipse (Addons/Polarization.py:45-92) on complex128 planes
+ * with double outputs [4][n]; same validation, eps and clamp. */
+int thz_stokes64_forward(const void* ex, const void* ey, long long n, double* out, thz_stream_t stream);
+int thz_polarization_ellipse64(const void* ex, const void* ey, long long n, double* out, thz_stream_t stream);
+
 /*
  * Per-step state of the graph-replayed trainers (not part of the reference: qat.py StepState, the
  * schedule values tau / s / beta, the device generator's seed and step, the multi-plane systems'
@@ -681,7 +717,8 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * "asm_cols_slice_adj", "asm_rows_inv"; the CZT z-x slice: "czt_slice_tables", "czt_slice_collapse",
  * "czt_slice_line"; its adjoint: "czt_slice_tables", "czt_slice_line_adj", "czt_slice_expand"; the
  * RSC z-x slice: "rsc_slice_rows", "rsc_slice_acc", "rsc_slice_line"; its adjoint: "rsc_slice_line_adj",
- * "rsc_slice_acc_adj", "rsc_slice_rows_adj"; ...).
+ * "rsc_slice_acc_adj", "rsc_slice_rows_adj"; the polarization entries: "stokes_fwd", "stokes_bwd",
+ * "polarization_ellipse", "stokes64_fwd", "polarization_ellipse64"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

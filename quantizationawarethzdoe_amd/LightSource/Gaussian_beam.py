@@ -89,7 +89,9 @@ class VectorialGuassian_beam(Guassian_beam):
         super().__init__(height, width, beam_waist_x, beam_waist_y, center, z_w0, alpha, wavelengths, spacing, device)
         jv = np.array(jones_vector) / np.linalg.norm(np.array(jones_vector))
         self.jones_vector = torch.tensor(jv, device=self.device)
-        self._jones = [float(np.float32(v)) for v in jv]
+        # a complex Jones vector (elliptical polarization, e.g. [1, 1 - 1j]) keeps its phase (:217-218,
+        # :310-316); a real one multiplies as the fp32 scalars it always did
+        self._jones = [complex(np.complex64(v)) if np.iscomplexobj(jv) else float(np.float32(v)) for v in jv]
 
     def forward(self) -> ElectricField:
         E = self._scalar_field()[0]

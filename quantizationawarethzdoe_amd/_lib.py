@@ -43,6 +43,8 @@ EXPORTED = [
     "thz_gaussian_beam", "thz_thin_lens", "thz_aperture",
     "thz_intensity_mse_workspace_size", "thz_intensity_mse_forward", "thz_intensity_mse_backward",
     "thz_resample_forward", "thz_resample_backward",
+    "thz_stokes_forward", "thz_stokes_backward", "thz_polarization_ellipse",
+    "thz_stokes64_forward", "thz_polarization_ellipse64",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -279,6 +281,10 @@ def _declare(lib):
                                                c_void_p, c_void_p]
     lib.thz_resample_forward.argtypes = [ctypes.POINTER(ResampleDesc), c_void_p, c_void_p, c_void_p]
     lib.thz_resample_backward.argtypes = [ctypes.POINTER(ResampleDesc), c_void_p, c_void_p, c_void_p]
+    for name in ("thz_stokes_forward", "thz_polarization_ellipse", "thz_stokes64_forward",
+                 "thz_polarization_ellipse64"):  # ex, ey, n, out, stream
+        getattr(lib, name).argtypes = [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]
+    lib.thz_stokes_backward.argtypes = [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,

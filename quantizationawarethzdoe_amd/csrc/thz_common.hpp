@@ -41,6 +41,10 @@ struct KernelTimer {
   void stop();
 };
 
+// Workgroups of a grid-stride streaming kernel on the current device: one per chunk of work, at
+// most 8 per compute unit (sized from the CU count, not from the data; thz_plan.hip)
+int stream_grid(long long chunks, int* blocks);
+
 // rows in-place-capable transforms of length n at row stride `stride` elements (thz_asm.hip)
 int fft_rows_strided(const void* in, void* out, int rows, int n, size_t stride, int inverse, hipStream_t s);
 // the shape rules and doubled grid Ph x Pw of the RSC planes (thz_asm.hip) and z-x slice (thz_rsc.hip)

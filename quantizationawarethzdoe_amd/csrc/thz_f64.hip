@@ -928,3 +928,91 @@ extern "C" int thz_czt64_forward(const thz_czt_desc64* d, const void* in, void* 
   kt.stop();
   return THZ_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Polarization analysis on complex128 planes (Addons/Polarization.py:45-92), the fp32 kernels of
+// thz_optics.hip in double: a pixel is already a 16-byte load per component, so one pixel per lane
+// in a grid-stride loop.  Same op order, eps and clamp of B's radicand.
+// ---------------------------------------------------------------------------------------------
+namespace thz {
+namespace f64 {
+
+constexpr int POL_THREADS = 256;
+constexpr double POL_EPS = 1e-6;
+
+struct StokesPx {
+  double I, Q, U, V;
+};
+__device__ __forceinline__ StokesPx stokes_px(double2 x, double2 y) {
+  const double xx = x.x * x.x + x.y * x.y, yy = y.x * y.x + y.y * y.y;
+  return StokesPx{xx + yy, xx - yy, 2.0 * (x.x * y.x + x.y * y.y), 2.0 * (x.y * y.x - x.x * y.y)};
+}
+
+__global__ void __launch_bounds__(POL_THREADS) stokes64_kernel(const double2* __restrict__ ex,
+                                                               const double2* __restrict__ ey, long long n,
+                                                               double* __restrict__ out) {
+  for (long long p = (long long)blockIdx.x * POL_THREADS + threadIdx.x; p < n; p += (long long)gridDim.x * POL_THREADS) {
+    const StokesPx s = stokes_px(ex[p], ey[p]);
+    out[p] = s.I;
+    out[n + p] = s.Q;
+    out[2 * n + p] = s.U;
+    out[3 * n + p] = s.V;
+  }
+}
+
+__global__ void __launch_bounds__(POL_THREADS) polarization_ellipse64_kernel(const double2* __restrict__ ex,
+                                                                             const double2* __restrict__ ey,
+                                                                             long long n, double* __restrict__ out) {
+  for (long long p = (long long)blockIdx.x * POL_THREADS + threadIdx.x; p < n; p += (long long)gridDim.x * POL_THREADS) {
+    const StokesPx s = stokes_px(ex[p], ey[p]);
+    const double Ip = sqrt((s.Q * s.Q + s.U * s.U) + s.V * s.V);
+    const double Lr = s.Q + POL_EPS;
+    const double aL = hypot(Lr, s.U);
+    const double rb = 0.5 * ((Ip - aL) + POL_EPS);
+    const double v = s.V + POL_EPS;
+    out[p] = sqrt(0.5 * ((Ip + aL) + POL_EPS));
+    out[n + p] = sqrt(rb < 0.0 ? 0.0 : rb);
+    out[2 * n + p] = 0.5 * atan2(s.U, Lr);
+    out[3 * n + p] = (double)((0.0 < v) - (v < 0.0));
+  }
+}
+
+static int pol_check(const char* who, const void* ex, const void* ey, const void* out, long long n) {
+  if (!ex || !ey || !out) return fail(THZ_E_ARG, "%s: null pointer", who);
+  if (((uintptr_t)ex | (uintptr_t)ey) & 15) return fail(THZ_E_ARG, "%s: complex plane not 16-byte aligned", who);
+  if ((uintptr_t)out & 7) return fail(THZ_E_ARG, "%s: real plane not 8-byte aligned", who);
+  if (n < 0) return fail(THZ_E_ARG, "%s: n = %lld < 0", who, n);
+  return THZ_OK;
+}
+
+}  // namespace f64
+}  // namespace thz
+
+extern "C" int thz_stokes64_forward(const void* ex, const void* ey, long long n, double* out, thz_stream_t stream) {
+  if (int e = f64::pol_check("thz_stokes64_forward", ex, ey, out, n)) return e;
+  if (n == 0) return THZ_OK;
+  int blocks = 0;
+  if (int e = stream_grid((n + f64::POL_THREADS - 1) / f64::POL_THREADS, &blocks)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  KernelTimer kt("stokes64_fwd", s);
+  hipLaunchKernelGGL(f64::stokes64_kernel, dim3((unsigned)blocks), dim3(f64::POL_THREADS), 0, s, (const double2*)ex,
+                     (const double2*)ey, n, out);
+  THZ_LAUNCH_CHECK();
+  kt.stop();
+  return THZ_OK;
+}
+
+extern "C" int thz_polarization_ellipse64(const void* ex, const void* ey, long long n, double* out,
+                                          thz_stream_t stream) {
+  if (int e = f64::pol_check("thz_polarization_ellipse64", ex, ey, out, n)) return e;
+  if (n == 0) return THZ_OK;
+  int blocks = 0;
+  if (int e = stream_grid((n + f64::POL_THREADS - 1) / f64::POL_THREADS, &blocks)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  KernelTimer kt("polarization_ellipse64", s);
+  hipLaunchKernelGGL(f64::polarization_ellipse64_kernel, dim3((unsigned)blocks), dim3(f64::POL_THREADS), 0, s,
+                     (const double2*)ex, (const double2*)ey, n, out);
+  THZ_LAUNCH_CHECK();
+  kt.stop();
+  return THZ_OK;
+}

@@ -12,6 +12,8 @@
 //                      max-path needs; the backward is then one elementwise pass.
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
+#include <initializer_list>
 
 #include "thz_common.hpp"
 #include "thz_dev.hpp"
@@ -426,6 +428,186 @@ __global__ void __launch_bounds__(64) step_fetch_kernel(const int* ring, int dep
   if (i == 0) counter[0] = k + 1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Polarization analysis of a vectorial field (Addons/Polarization.py:45-92): the Stokes vector, its
+// backward and the ellipse parameters, one streaming pass each over the Ex and Ey planes (the Ez
+// plane is never read).  Memory-bound: 16 B read and 16 B written per pixel (backward: 32 + 16).
+// A lane owns four pixels per round of the grid-stride loop.  WIDE: four consecutive pixels, two
+// 16-byte loads per component and one 16-byte store per output plane -- the host picks it only when
+// every pointer is 16-byte aligned and n % 4 == 0 (the Ey plane of a contiguous [3, C, H, W] tensor
+// with an odd plane starts 8-byte aligned, and so do output planes 1-3 when n is odd).  Otherwise
+// the same body with element-width accesses, the lane's pixels a workgroup apart (coalesced).  A
+// group that crosses n is moved pixel by pixel under a bound check in either form.  The arithmetic
+// is per pixel and this unit compiles with contraction off, so both forms give the same bits.
+// ---------------------------------------------------------------------------------------------
+constexpr int POL_THREADS = 256;
+constexpr int POL_PX = 4;  // pixels per lane per round
+constexpr int POL_CHUNK = POL_THREADS * POL_PX;
+constexpr float POL_EPS = 1e-6f;  // Addons/Polarization.py:17
+
+template <bool WIDE>
+struct PolLane {
+  long long p0, n;
+  bool full;  // the four pixels are consecutive, inside n and moved as 16-byte accesses
+  __device__ __forceinline__ PolLane(long long c0, long long n_) : n(n_) {
+    p0 = c0 + (WIDE ? POL_PX * (long long)threadIdx.x : (long long)threadIdx.x);
+    full = WIDE && p0 + (POL_PX - 1) < n;
+  }
+  __device__ __forceinline__ long long at(int k) const { return p0 + (WIDE ? k : k * POL_THREADS); }
+  __device__ __forceinline__ void load(const float2* __restrict__ a, float2 v[POL_PX]) const {
+    if (full) {
+      const float4* q = reinterpret_cast<const float4*>(a + p0);
+      const float4 f0 = q[0], f1 = q[1];
+      v[0] = make_float2(f0.x, f0.y); v[1] = make_float2(f0.z, f0.w);
+      v[2] = make_float2(f1.x, f1.y); v[3] = make_float2(f1.z, f1.w);
+    } else {
+#pragma unroll
+      for (int k = 0; k < POL_PX; ++k) v[k] = at(k) < n ? a[at(k)] : make_float2(0.f, 0.f);
+    }
+  }
+  __device__ __forceinline__ void load(const float* __restrict__ a, float v[POL_PX]) const {
+    if (full) {
+      const float4 f = *reinterpret_cast<const float4*>(a + p0);
+      v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < POL_PX; ++k) v[k] = at(k) < n ? a[at(k)] : 0.f;
+    }
+  }
+  __device__ __forceinline__ void store(float2* __restrict__ a, const float2 v[POL_PX]) const {
+    if (full) {
+      float4* q = reinterpret_cast<float4*>(a + p0);
+      q[0] = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
+      q[1] = make_float4(v[2].x, v[2].y, v[3].x, v[3].y);
+    } else {
+#pragma unroll
+      for (int k = 0; k < POL_PX; ++k)
+        if (at(k) < n) a[at(k)] = v[k];
+    }
+  }
+  __device__ __forceinline__ void store(float* __restrict__ a, const float v[POL_PX]) const {
+    if (full) {
+      *reinterpret_cast<float4*>(a + p0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < POL_PX; ++k)
+        if (at(k) < n) a[at(k)] = v[k];
+    }
+  }
+};
+
+struct StokesPx {
+  float I, Q, U, V;
+};
+// Ex conj(Ey) = (a + ib)(c - id) = (ac + bd) + i (bc - ad)   (:53-56)
+__device__ __forceinline__ StokesPx stokes_px(float2 x, float2 y) {
+  const float xx = x.x * x.x + x.y * x.y, yy = y.x * y.x + y.y * y.y;
+  return StokesPx{xx + yy, xx - yy, 2.f * (x.x * y.x + x.y * y.y), 2.f * (x.y * y.x - x.x * y.y)};
+}
+
+template <bool WIDE>
+__global__ void __launch_bounds__(POL_THREADS) stokes_fwd_kernel(const float2* __restrict__ ex,
+                                                                 const float2* __restrict__ ey, long long n,
+                                                                 float* __restrict__ out) {
+  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < n; c0 += (long long)gridDim.x * POL_CHUNK) {
+    const PolLane<WIDE> L(c0, n);
+    float2 x[POL_PX], y[POL_PX];
+    L.load(ex, x);
+    L.load(ey, y);
+    float o[4][POL_PX];
+#pragma unroll
+    for (int k = 0; k < POL_PX; ++k) {
+      const StokesPx s = stokes_px(x[k], y[k]);
+      o[0][k] = s.I; o[1][k] = s.Q; o[2][k] = s.U; o[3][k] = s.V;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) L.store(out + q * n, o[q]);
+  }
+}
+
+// The cotangent of a real loss, torch's convention (dL/dRe + i dL/dIm).  With Ex = a + ib, Ey = c + id:
+// dI = 2 Ex, dQ = 2 Ex, dU = 2 (c + id) = 2 Ey, dV = 2 (-d + ic) = 2i Ey towards Ex, and
+// dI = 2 Ey, dQ = -2 Ey, dU = 2 Ex, dV = 2 (b - ia) = -2i Ex towards Ey, so
+//   gEx = 2 [(gI + gQ) Ex + (gU + i gV) Ey],   gEy = 2 [(gI - gQ) Ey + (gU - i gV) Ex]
+template <bool WIDE>
+__global__ void __launch_bounds__(POL_THREADS) stokes_bwd_kernel(const float2* __restrict__ ex,
+                                                                 const float2* __restrict__ ey, long long n,
+                                                                 const float* __restrict__ g,
+                                                                 float2* __restrict__ gex, float2* __restrict__ gey) {
+  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < n; c0 += (long long)gridDim.x * POL_CHUNK) {
+    const PolLane<WIDE> L(c0, n);
+    float2 x[POL_PX], y[POL_PX], gx[POL_PX], gy[POL_PX];
+    float gs[4][POL_PX];
+    L.load(ex, x);
+    L.load(ey, y);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) L.load(g + q * n, gs[q]);
+#pragma unroll
+    for (int k = 0; k < POL_PX; ++k) {
+      const float sa = gs[0][k] + gs[1][k], sb = gs[0][k] - gs[1][k], gU = gs[2][k], gV = gs[3][k];
+      gx[k] = make_float2(2.f * (sa * x[k].x + (gU * y[k].x - gV * y[k].y)),
+                          2.f * (sa * x[k].y + (gU * y[k].y + gV * y[k].x)));
+      gy[k] = make_float2(2.f * (sb * y[k].x + (gU * x[k].x + gV * x[k].y)),
+                          2.f * (sb * y[k].y + (gU * x[k].y - gV * x[k].x)));
+    }
+    L.store(gex, gx);
+    L.store(gey, gy);
+  }
+}
+
+// polarization_ellipse (:72-84) in the reference's op order, fp32: L = Q + 1j U + eps adds eps to
+// the real part; torch.abs of a complex is hypot.  B's radicand is clamped at 0 (rounding leaves it
+// slightly negative on exactly linear polarization, where the reference returns NaN); a NaN stays NaN.
+__device__ __forceinline__ void ellipse_px(float2 x, float2 y, float* A, float* B, float* th, float* h) {
+  const StokesPx s = stokes_px(x, y);
+  const float Ip = sqrtf((s.Q * s.Q + s.U * s.U) + s.V * s.V);
+  const float Lr = s.Q + POL_EPS;
+  const float aL = hypotf(Lr, s.U);
+  const float rb = 0.5f * ((Ip - aL) + POL_EPS);
+  *A = sqrtf(0.5f * ((Ip + aL) + POL_EPS));
+  *B = sqrtf(rb < 0.f ? 0.f : rb);
+  *th = 0.5f * atan2f(s.U, Lr);
+  const float v = s.V + POL_EPS;
+  *h = (float)((0.f < v) - (v < 0.f));
+}
+
+template <bool WIDE>
+__global__ void __launch_bounds__(POL_THREADS) polarization_ellipse_kernel(const float2* __restrict__ ex,
+                                                                           const float2* __restrict__ ey,
+                                                                           long long n, float* __restrict__ out) {
+  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < n; c0 += (long long)gridDim.x * POL_CHUNK) {
+    const PolLane<WIDE> L(c0, n);
+    float2 x[POL_PX], y[POL_PX];
+    L.load(ex, x);
+    L.load(ey, y);
+    float o[4][POL_PX];
+#pragma unroll
+    for (int k = 0; k < POL_PX; ++k) ellipse_px(x[k], y[k], &o[0][k], &o[1][k], &o[2][k], &o[3][k]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) L.store(out + q * n, o[q]);
+  }
+}
+
+static bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+// host validation shared by the polarization entries: cplx are complex64 planes, real float planes
+static int pol_check(const char* who, std::initializer_list<const void*> cplx, std::initializer_list<const void*> real,
+                     long long n, bool* wide) {
+  *wide = n % POL_PX == 0;
+  for (const void* p : cplx) {
+    if (!p) return fail(THZ_E_ARG, "%s: null pointer", who);
+    if (misaligned(p, sizeof(float2))) return fail(THZ_E_ARG, "%s: complex plane not 8-byte aligned", who);
+    *wide = *wide && !misaligned(p, 16);
+  }
+  for (const void* p : real) {
+    if (!p) return fail(THZ_E_ARG, "%s: null pointer", who);
+    if (misaligned(p, sizeof(float))) return fail(THZ_E_ARG, "%s: real plane not 4-byte aligned", who);
+    *wide = *wide && !misaligned(p, 16);  // with n % 4 == 0 planes 1-3 are aligned as plane 0 is
+  }
+  if (n < 0) return fail(THZ_E_ARG, "%s: n = %lld < 0", who, n);
+  return THZ_OK;
+}
+
 }  // namespace thz
 
 using namespace thz;
@@ -663,4 +845,56 @@ extern "C" int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* param
   THZ_LAUNCH_CHECK();
   kt.stop();
   return THZ_OK;
+}
+
+// PolarizationAnalyser.polarization_state / polarization_ellipse (Addons/Polarization.py:45-92) and
+// the Stokes vector's backward.  Validation is host-only and comes before any device call.
+template <class Launch>
+static int pol_launch(const char* timer, long long n, hipStream_t s, Launch&& launch) {
+  if (n == 0) return THZ_OK;
+  int blocks = 0;
+  if (int e = stream_grid((n + POL_CHUNK - 1) / POL_CHUNK, &blocks)) return e;
+  KernelTimer kt(timer, s);
+  launch(dim3((unsigned)blocks), dim3(POL_THREADS));
+  THZ_LAUNCH_CHECK();
+  kt.stop();
+  return THZ_OK;
+}
+
+extern "C" int thz_stokes_forward(const void* ex, const void* ey, long long n, float* out, thz_stream_t stream) {
+  bool wide;
+  if (int e = pol_check("thz_stokes_forward", {ex, ey}, {out}, n, &wide)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  return pol_launch("stokes_fwd", n, s, [&](dim3 g, dim3 b) {
+    if (wide) hipLaunchKernelGGL(stokes_fwd_kernel<true>, g, b, 0, s, (const float2*)ex, (const float2*)ey, n, out);
+    else hipLaunchKernelGGL(stokes_fwd_kernel<false>, g, b, 0, s, (const float2*)ex, (const float2*)ey, n, out);
+  });
+}
+
+extern "C" int thz_stokes_backward(const void* ex, const void* ey, long long n, const float* grad, void* gex,
+                                   void* gey, thz_stream_t stream) {
+  bool wide;
+  if (int e = pol_check("thz_stokes_backward", {ex, ey, gex, gey}, {grad}, n, &wide)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  return pol_launch("stokes_bwd", n, s, [&](dim3 g, dim3 b) {
+    if (wide)
+      hipLaunchKernelGGL(stokes_bwd_kernel<true>, g, b, 0, s, (const float2*)ex, (const float2*)ey, n, grad,
+                         (float2*)gex, (float2*)gey);
+    else
+      hipLaunchKernelGGL(stokes_bwd_kernel<false>, g, b, 0, s, (const float2*)ex, (const float2*)ey, n, grad,
+                         (float2*)gex, (float2*)gey);
+  });
+}
+
+extern "C" int thz_polarization_ellipse(const void* ex, const void* ey, long long n, float* out,
+                                        thz_stream_t stream) {
+  bool wide;
+  if (int e = pol_check("thz_polarization_ellipse", {ex, ey}, {out}, n, &wide)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  return pol_launch("polarization_ellipse", n, s, [&](dim3 g, dim3 b) {
+    if (wide)
+      hipLaunchKernelGGL(polarization_ellipse_kernel<true>, g, b, 0, s, (const float2*)ex, (const float2*)ey, n, out);
+    else
+      hipLaunchKernelGGL(polarization_ellipse_kernel<false>, g, b, 0, s, (const float2*)ex, (const float2*)ey, n, out);
+  });
 }

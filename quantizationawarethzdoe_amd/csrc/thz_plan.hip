@@ -82,6 +82,27 @@ int get_plan(int n, FftPlan* out) {
   return THZ_OK;
 }
 
+int stream_grid(long long chunks, int* blocks) {
+  static std::mutex mu;
+  static std::map<int, int> cus_of;  // device -> compute units
+  int dev = 0;
+  THZ_HIP_CHECK(hipGetDevice(&dev));
+  int cus = 0;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cus_of.find(dev);
+    if (it == cus_of.end()) {
+      THZ_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+      if (cus < 1) return fail(THZ_E_HIP, "device %d reports %d compute units", dev, cus);
+      it = cus_of.emplace(dev, cus).first;
+    }
+    cus = it->second;
+  }
+  const long long cap = 8LL * cus;
+  *blocks = (int)(chunks < 1 ? 1 : chunks < cap ? chunks : cap);
+  return THZ_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // per-kernel event timing
 // ---------------------------------------------------------------------------------------------
