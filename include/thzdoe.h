@@ -25,6 +25,8 @@
  *   thz_quant_*      Components/QuantizedDOE.py:181-1388 quantized height maps (+ backward)
  *   thz_fft_*        utils/Helper_Functions.py:99-160 ft2/ift2 (centred ortho FFT)
  *   thz_stokes_*, thz_polarization_ellipse*  Addons/Polarization.py:45-92  PolarizationAnalyser
+ *   thz_noise_*, thz_signal_scale*, thz_snr_noise_backward  Addons/Noise.py:4-112, utils/Noise.py:4-116,
+ *                    utils/Helper_Functions.py:258-366  the detector noise models
  */
 #ifndef THZDOE_H_
 #define THZDOE_H_
@@ -62,7 +64,9 @@ typedef void* thz_stream_t; /* hipStream_t */
  * thz_rsc_slice_workspace_size and thz_rsc_slice_forward with their new thz_rsc_slice_desc, and
  * thz_rsc_slice_adjoint_workspace_size and thz_rsc_slice_adjoint on the same descriptor, and the
  * descriptor-free polarization entries thz_stokes_forward, thz_stokes_backward,
- * thz_polarization_ellipse, thz_stokes64_forward and thz_polarization_ellipse64):
+ * thz_polarization_ellipse, thz_stokes64_forward and thz_polarization_ellipse64, and the noise
+ * entries thz_noise_apply (with its new thz_noise_desc), thz_noise_draws,
+ * thz_signal_scale_workspace_size, thz_signal_scale and thz_snr_noise_backward):
  * a caller compares thz_abi_version()
  * with the THZ_ABI_VERSION it was compiled against before its first call, since a shorter
  * struct from an older header would make the library read past it.  Descriptors are plain C
@@ -604,6 +608,91 @@ int thz_stokes_backward(const void* ex, const void* ey, long long n, const float
 int thz_polarization_ellipse(const void* ex, const void* ey, long long n, float* out, thz_stream_t stream);
 
 /*
+ * Detector noise models (Addons/Noise.py:4-112, utils/Noise.py:4-116, utils/Helper_Functions.py:
+ * 258-366: GaussianNoise, PoissonNoise, PoissonGaussianNoise, UniformNoise) on the counter-based
+ * device generator of thz_doe_desc.rng: every draw is a hash of (seed, step, stream, element
+ * index), so a call is reproducible from its state, independent of the launch geometry, and a
+ * captured graph draws afresh on every replay once its host advances rng[1].  No torch RNG kernel
+ * and no host synchronisation anywhere.  fp32 / complex64 only.
+ *
+ * thz_noise_apply: one streaming pass, out[i] = model(in[i]) for i < n, fp32 in the reference's
+ * operation order (x is in[i], or |in[i]|^2 = abs() ** 2 for THZ_NOISE_IN_FIELD_INTENSITY):
+ *   THZ_NOISE_GAUSS          x + n sigma                              (Addons/Noise.py:27)
+ *   THZ_NOISE_UNIFORM        x + (u - 0.5) 2 a                        (:112)
+ *   THZ_NOISE_POISSON        poisson(x / gain), then * gain if normalize   (:58-61)
+ *   THZ_NOISE_POISSON_GAUSS  poisson(x / gain) gain + n sigma         (:87-89)
+ * n is a standard normal (Box-Muller on two 24-bit uniforms, |n| <= 5.77), u is U[0, 1) with 24
+ * bits, both drawn at (stream, i); the Poisson draw of element i reads a 64-bit sequence of its
+ * own, seeded by a hash of (stream, i) and advanced per attempt, that its n never touches and
+ * that two streams do not share (inversion below a rate of 10, transformed rejection PTRS from
+ * 10; rates up to 2^24, where fp32 still holds every count; a rate of 0 gives 0, a negative or
+ * NaN rate gives NaN -- no host check, that would be a sync).  Streams are independent under one
+ * seed: the generator mixes the stream into the seed word (seed ^ stream * 0x9E3779B9), so two
+ * (seed, stream) pairs with the same mix draw the same values.  THZ_NOISE_IN_COMPLEX64 (GAUSS only): in and out are complex64 and n is a complex
+ * normal of total variance 1 (torch.randn_like of a complex tensor), both Box-Muller outputs of
+ * the element's word.  sigma_dev, when not NULL, is a device scalar read in place of sigma (the
+ * SNR form, utils/Noise.py:28-32, with thz_signal_scale's output).
+ * in: n floats (REAL32) or n complex64 (FIELD_INTENSITY, COMPLEX64); out: n floats, or n
+ * complex64 for COMPLEX64; in and out do not overlap.  When both
+ * pointers are 16-byte aligned and n % 4 == 0 a lane moves four elements per 16-byte access;
+ * otherwise the same body runs at element width (bit-identical results).
+ * Null pointers (d, in, out, d->rng), n < 0, n > 2^32 (the generator's index is 32-bit), an unknown
+ * kind or input, COMPLEX64 with a kind other than GAUSS and gain <= 0 for the Poisson kinds are
+ * THZ_E_ARG; n == 0 is THZ_OK and launches nothing.
+ */
+#define THZ_NOISE_GAUSS 0
+#define THZ_NOISE_UNIFORM 1
+#define THZ_NOISE_POISSON 2
+#define THZ_NOISE_POISSON_GAUSS 3
+#define THZ_NOISE_IN_REAL32 0
+#define THZ_NOISE_IN_FIELD_INTENSITY 1
+#define THZ_NOISE_IN_COMPLEX64 2
+typedef struct thz_noise_desc {
+  int kind;                /* THZ_NOISE_* */
+  int input;               /* THZ_NOISE_IN_* */
+  float sigma, a, gain;
+  int normalize;           /* POISSON: multiply the counts by gain */
+  const float* sigma_dev;  /* device [1] or NULL: replaces sigma */
+  const unsigned* rng;     /* device [2] = {seed, step} */
+  unsigned stream;
+} thz_noise_desc;
+int thz_noise_apply(const thz_noise_desc* d, const void* in, void* out, long long n, thz_stream_t stream);
+
+/*
+ * The raw draws thz_noise_apply uses for elements 0 .. n-1 of (rng, stream), so a caller can hold
+ * the kernels to the reference's formulas exactly: THZ_DRAW_NORMAL out[n] = n_i, THZ_DRAW_UNIFORM
+ * out[n] = u_i, THZ_DRAW_COMPLEX_NORMAL out[2 n] = (Re, Im) of the complex normal, interleaved.
+ * Validation as thz_noise_apply.
+ */
+#define THZ_DRAW_NORMAL 0
+#define THZ_DRAW_UNIFORM 1
+#define THZ_DRAW_COMPLEX_NORMAL 2
+int thz_noise_draws(int what, const unsigned* rng, unsigned stream, long long n, float* out, thz_stream_t stream_handle);
+
+/*
+ * The noise amplitude of the SNR form of GaussianNoise (utils/Noise.py:28-32):
+ *   scale[0] = sqrt(mean(|x|^2) / snr_linear),  snr_linear = 10 ** (SNR_dB / 10),
+ * x: n floats (is_complex == 0) or n complex64, scale: a device scalar (feed it to
+ * thz_noise_desc.sigma_dev).  Summed in fp64 and rounded to fp32 once, in two stages: one partial
+ * per workgroup in the workspace (a grid that depends on n alone), then one workgroup adds the
+ * partials in a fixed order -- the same input always gives the same bits.  No host sync.
+ * Null pointers, n < 0, n > 2^32 and snr_linear <= 0 are THZ_E_ARG; a workspace below
+ * thz_signal_scale_workspace_size(n) is THZ_E_WORKSPACE; n == 0 is THZ_OK and launches nothing.
+ *
+ * thz_snr_noise_backward: the cotangent of y = x + n scale(x) (torch's convention for complex x),
+ * the noise regenerated from (rng, stream):
+ *   gx = g + x S / (N snr_linear scale),  S = sum_i Re(conj(g_i) n_i),
+ * S reduced in fp64 as above.  g, x and gx have x's element type; scale is thz_signal_scale's
+ * output for this x; same workspace size.
+ */
+int thz_signal_scale_workspace_size(long long n, size_t* bytes);
+int thz_signal_scale(const void* x, long long n, int is_complex, float snr_linear, float* scale, void* workspace,
+                     size_t bytes, thz_stream_t stream);
+int thz_snr_noise_backward(const void* g, const void* x, long long n, int is_complex, float snr_linear,
+                           const float* scale, const unsigned* rng, unsigned stream, void* gx, void* workspace,
+                           size_t bytes, thz_stream_t stream_handle);
+
+/*
  * Batched 1-D FFT along the contiguous axis (the building block of ft2/ift2,
  * utils/Helper_Functions.py:150, without shifts): in/out [rows, n], unnormalised,
  * inverse != 0 for the backward transform.  n <= 16384, any factorisation.
@@ -718,7 +807,9 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * "czt_slice_line"; its adjoint: "czt_slice_tables", "czt_slice_line_adj", "czt_slice_expand"; the
  * RSC z-x slice: "rsc_slice_rows", "rsc_slice_acc", "rsc_slice_line"; its adjoint: "rsc_slice_line_adj",
  * "rsc_slice_acc_adj", "rsc_slice_rows_adj"; the polarization entries: "stokes_fwd", "stokes_bwd",
- * "polarization_ellipse", "stokes64_fwd", "polarization_ellipse64"; ...).
+ * "polarization_ellipse", "stokes64_fwd", "polarization_ellipse64"; the noise entries: "noise_apply",
+ * "noise_draws", "signal_scale_part", "signal_scale_finish", "snr_noise_bwd_part", "snr_noise_bwd_finish",
+ * "snr_noise_bwd"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

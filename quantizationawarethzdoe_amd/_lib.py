@@ -45,6 +45,8 @@ EXPORTED = [
     "thz_resample_forward", "thz_resample_backward",
     "thz_stokes_forward", "thz_stokes_backward", "thz_polarization_ellipse",
     "thz_stokes64_forward", "thz_polarization_ellipse64",
+    "thz_noise_apply", "thz_noise_draws", "thz_signal_scale_workspace_size", "thz_signal_scale",
+    "thz_snr_noise_backward",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -196,6 +198,18 @@ class ResampleDesc(ctypes.Structure):
                 ("dx_out", ctypes.c_float), ("dy_out", ctypes.c_float)]
 
 
+class NoiseDesc(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("input", ctypes.c_int),
+                ("sigma", ctypes.c_float), ("a", ctypes.c_float), ("gain", ctypes.c_float),
+                ("normalize", ctypes.c_int),
+                ("sigma_dev", ctypes.c_void_p),  # const float* device [1], NULL = the host sigma
+                ("rng", ctypes.c_void_p), ("stream", ctypes.c_uint)]
+
+
+NOISE_GAUSS, NOISE_UNIFORM, NOISE_POISSON, NOISE_POISSON_GAUSS = 0, 1, 2, 3
+NOISE_IN_REAL32, NOISE_IN_FIELD_INTENSITY, NOISE_IN_COMPLEX64 = 0, 1, 2
+DRAW_NORMAL, DRAW_UNIFORM, DRAW_COMPLEX_NORMAL = 0, 1, 2
+
 THZ_MAX_ADAM_PARAMS = 16
 
 
@@ -285,6 +299,13 @@ def _declare(lib):
                  "thz_polarization_ellipse64"):  # ex, ey, n, out, stream
         getattr(lib, name).argtypes = [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]
     lib.thz_stokes_backward.argtypes = [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]
+    c_ll, c_uint, c_float = ctypes.c_longlong, ctypes.c_uint, ctypes.c_float
+    lib.thz_noise_apply.argtypes = [ctypes.POINTER(NoiseDesc), c_void_p, c_void_p, c_ll, c_void_p]
+    lib.thz_noise_draws.argtypes = [c_int, c_void_p, c_uint, c_ll, c_void_p, c_void_p]
+    lib.thz_signal_scale_workspace_size.argtypes = [c_ll, ctypes.POINTER(c_size_t)]
+    lib.thz_signal_scale.argtypes = [c_void_p, c_ll, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_snr_noise_backward.argtypes = [c_void_p, c_void_p, c_ll, c_int, c_float, c_void_p, c_void_p, c_uint,
+                                           c_void_p, c_void_p, c_size_t, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,

@@ -1,6 +1,7 @@
 // The host launch toolkit of the propagator units (thz_asm.hip, thz_rsc.hip, thz_czt.hip, thz_f64.hip):
 // the list of instantiated transform sizes and its dispatchers, workgroup sizes, the workspace
-// alignment and check, the large-LDS opt-in.  Host code only; include after thz_common.hpp.
+// alignment and check, the large-LDS opt-in.  The noise unit (thz_noise.hip) takes the workspace
+// alignment and check from it.  Host code only; include after thz_common.hpp.
 #pragma once
 #include <type_traits>
 #include <vector>

@@ -432,69 +432,14 @@ __global__ void __launch_bounds__(64) step_fetch_kernel(const int* ring, int dep
 // Polarization analysis of a vectorial field (Addons/Polarization.py:45-92): the Stokes vector, its
 // backward and the ellipse parameters, one streaming pass each over the Ex and Ey planes (the Ez
 // plane is never read).  Memory-bound: 16 B read and 16 B written per pixel (backward: 32 + 16).
-// A lane owns four pixels per round of the grid-stride loop.  WIDE: four consecutive pixels, two
-// 16-byte loads per component and one 16-byte store per output plane -- the host picks it only when
-// every pointer is 16-byte aligned and n % 4 == 0 (the Ey plane of a contiguous [3, C, H, W] tensor
-// with an odd plane starts 8-byte aligned, and so do output planes 1-3 when n is odd).  Otherwise
-// the same body with element-width accesses, the lane's pixels a workgroup apart (coalesced).  A
-// group that crosses n is moved pixel by pixel under a bound check in either form.  The arithmetic
-// is per pixel and this unit compiles with contraction off, so both forms give the same bits.
+// The kernels run on the streaming lane of thz_dev.hpp (PolLane, POL_THREADS / POL_PX / POL_CHUNK,
+// described there and shared with thz_noise.hip): two 16-byte loads per component and one 16-byte
+// store per output plane in the wide form, which pol_check picks only when every pointer is 16-byte
+// aligned and n % 4 == 0 (the Ey plane of a contiguous [3, C, H, W] tensor with an odd plane starts
+// 8-byte aligned, and so do output planes 1-3 when n is odd).  The arithmetic is per pixel and this
+// unit compiles with contraction off, so both forms give the same bits.
 // ---------------------------------------------------------------------------------------------
-constexpr int POL_THREADS = 256;
-constexpr int POL_PX = 4;  // pixels per lane per round
-constexpr int POL_CHUNK = POL_THREADS * POL_PX;
 constexpr float POL_EPS = 1e-6f;  // Addons/Polarization.py:17
-
-template <bool WIDE>
-struct PolLane {
-  long long p0, n;
-  bool full;  // the four pixels are consecutive, inside n and moved as 16-byte accesses
-  __device__ __forceinline__ PolLane(long long c0, long long n_) : n(n_) {
-    p0 = c0 + (WIDE ? POL_PX * (long long)threadIdx.x : (long long)threadIdx.x);
-    full = WIDE && p0 + (POL_PX - 1) < n;
-  }
-  __device__ __forceinline__ long long at(int k) const { return p0 + (WIDE ? k : k * POL_THREADS); }
-  __device__ __forceinline__ void load(const float2* __restrict__ a, float2 v[POL_PX]) const {
-    if (full) {
-      const float4* q = reinterpret_cast<const float4*>(a + p0);
-      const float4 f0 = q[0], f1 = q[1];
-      v[0] = make_float2(f0.x, f0.y); v[1] = make_float2(f0.z, f0.w);
-      v[2] = make_float2(f1.x, f1.y); v[3] = make_float2(f1.z, f1.w);
-    } else {
-#pragma unroll
-      for (int k = 0; k < POL_PX; ++k) v[k] = at(k) < n ? a[at(k)] : make_float2(0.f, 0.f);
-    }
-  }
-  __device__ __forceinline__ void load(const float* __restrict__ a, float v[POL_PX]) const {
-    if (full) {
-      const float4 f = *reinterpret_cast<const float4*>(a + p0);
-      v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < POL_PX; ++k) v[k] = at(k) < n ? a[at(k)] : 0.f;
-    }
-  }
-  __device__ __forceinline__ void store(float2* __restrict__ a, const float2 v[POL_PX]) const {
-    if (full) {
-      float4* q = reinterpret_cast<float4*>(a + p0);
-      q[0] = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
-      q[1] = make_float4(v[2].x, v[2].y, v[3].x, v[3].y);
-    } else {
-#pragma unroll
-      for (int k = 0; k < POL_PX; ++k)
-        if (at(k) < n) a[at(k)] = v[k];
-    }
-  }
-  __device__ __forceinline__ void store(float* __restrict__ a, const float v[POL_PX]) const {
-    if (full) {
-      *reinterpret_cast<float4*>(a + p0) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < POL_PX; ++k)
-        if (at(k) < n) a[at(k)] = v[k];
-    }
-  }
-};
 
 struct StokesPx {
   float I, Q, U, V;

@@ -110,3 +110,8 @@ def DOE_xyz_cordinates_Generator(height_map, dxy, new_dxy=0.001, origin='center'
     xyz = np.stack([xc.flatten(), yc.flatten(), z], axis=-1).reshape(-1, 3)
     np.savetxt(f"DOE_xyz_coordinates_{datetime.now().strftime('%Y%m%d-%H%M%S')}.csv", xyz, delimiter=",")
     return xyz
+
+
+# the noise models the reference repeats here (utils/Helper_Functions.py:258-366, the sigma forms)
+from quantizationawarethzdoe_amd.Addons.Noise import (GaussianNoise, PoissonGaussianNoise, PoissonNoise,  # noqa: E402,F401
+                                                      UniformNoise)
