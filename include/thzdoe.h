@@ -693,6 +693,87 @@ int thz_snr_noise_backward(const void* g, const void* x, long long n, int is_com
                            size_t bytes, thz_stream_t stream_handle);
 
 /*
+ * The image losses of utils/losses.py on contiguous float32 device arrays (thz_losses.hip).
+ *
+ * Dice and BCE (BinaryDiceLoss utils/losses.py:21-44, BinaryCEloss utils/losses.py:48-58) share one
+ * streaming pass over pred, target viewed as [N, M].  thz_dice_bce_sums writes sums[N][4] (double):
+ *   sum p t,  sum p^e,  sum t^e  (utils/losses.py:32-33; e = p of the descriptor, 1 and 2 without powf)
+ *   sum bce(p, t),  bce = max(x, 0) - x t + log1p(exp(-|x|))  (torch.nn.BCEWithLogitsLoss, utils/losses.py:54);
+ * with weight / pos_weight (device [N M], either may be NULL) torch's
+ *   ((1 - t) x + (1 + (pos_weight - 1) t) (log1p(exp(-|x|)) + max(-x, 0))) weight.
+ * terms selects what is formed (a sum that is not is 0); bce_map (device [N M] or NULL) also receives
+ * the elementwise BCE (reduction='none').  fp64 partial per workgroup in the workspace, on a grid
+ * that depends on (N, M) alone, then a finish kernel adds the partials in index order: no atomics,
+ * the same input gives the same bits, aligned or not.  16-byte accesses when every pointer is
+ * 16-byte aligned and M % 4 == 0, the same body at element width otherwise.
+ *
+ * thz_dice_bce_backward writes grad_pred [N M] in one pass from the saved sums and the upstream
+ * gradients, which stay on the device (no host sync):
+ *   DICE: g_dice[n] d/dp (1 - num / den) = -g_dice[n] (t den - num e p^(e-1)) / den^2,
+ *         num = sum p t + smooth, den = sum p^e + sum t^e + smooth  (utils/losses.py:32-35)
+ *   BCE:  g_bce (sigma(x) - t), weighted  g_bce weight ((1 - t) - (1 + (pos_weight - 1) t) (1 - sigma(x)));
+ *         g_bce is a device scalar, or [N M] when bce_grad_elementwise (reduction='none').
+ * Both terms in one pass when terms has both (Hierarchyloss, utils/losses.py:86-88).
+ * A null descriptor or pointer, N < 1, M < 1 and terms outside DICE | BCE are THZ_E_ARG; N > 2^24 is
+ * THZ_E_UNSUPPORTED; a workspace below thz_dice_bce_sums_workspace_size is THZ_E_WORKSPACE.
+ */
+#define THZ_LOSS_TERM_DICE 1
+#define THZ_LOSS_TERM_BCE 2
+typedef struct thz_dice_bce_desc {
+  long long N, M;
+  float p;                   /* the Dice exponent (utils/losses.py:21: 2) */
+  float smooth;              /* utils/losses.py:21: 1 (backward only; the sums carry no smooth) */
+  int terms;                 /* THZ_LOSS_TERM_DICE | THZ_LOSS_TERM_BCE */
+  int bce_grad_elementwise;  /* backward: g_bce is [N M] */
+  const float* weight;       /* device [N M] or NULL */
+  const float* pos_weight;   /* device [N M] or NULL */
+} thz_dice_bce_desc;
+int thz_dice_bce_sums_workspace_size(const thz_dice_bce_desc* d, size_t* bytes);
+int thz_dice_bce_sums(const thz_dice_bce_desc* d, const float* pred, const float* target, double* sums,
+                      float* bce_map, void* workspace, size_t bytes, thz_stream_t stream);
+int thz_dice_bce_backward(const thz_dice_bce_desc* d, const float* pred, const float* target, const double* sums,
+                          const float* g_dice, const float* g_bce, float* grad_pred, thz_stream_t stream);
+
+/*
+ * SSIM (SSIMloss utils/losses.py:62-74, which wraps pytorch_msssim.SSIM) of x, y [NC][H][W]: the
+ * mean over the window positions [H - ws + 1][W - ws + 1] of
+ *   S = A1 A2 / (B1 B2),  A1 = 2 mu_x mu_y + C1,  A2 = 2 sigma_xy + C2,
+ *   B1 = mu_x^2 + mu_y^2 + C1,  B2 = sigma_x^2 + sigma_y^2 + C2,
+ *   sigma_x^2 = m_xx - mu_x^2,  sigma_xy = m_xy - mu_x mu_y,  C1 = (K1 L)^2,  C2 = (K2 L)^2,
+ * mu, m the separable window's means of x, y, x^2, y^2, xy.  window: the ws taps of the 1-D window,
+ * formed by the caller (pytorch_msssim: exp(-(i - ws / 2)^2 / (2 sigma^2)) normalised in fp32); ws odd,
+ * 1 .. THZ_SSIM_MAX_WIN, anything else THZ_E_UNSUPPORTED.  The kernels filter in fp64 with the taps
+ * divided by their own fp64 sum: fp32-normalised taps sum to 1 + delta (|delta| ~ 1e-8), which exact
+ * arithmetic would turn into a variance of -delta x^2 on a flat region, amplified by 1 / C2 into S;
+ * fp32 arithmetic never resolves delta and the definition has none.  An axis shorter than ws is not filtered
+ * (one tap of 1 on it), as pytorch_msssim does.  One workgroup per 32 x 32 tile of positions stages
+ * its tiles of x and y in LDS once and filters in fp64; ssim[NC] (relu'd when nonnegative) and cs[NC]
+ * (the mean of A2 / B2; may be NULL) come from fp64 partials per workgroup added in index order.
+ * coef (device [3][NC][H'][W'] or NULL) receives a = dS/dmu_x, b = dS/dm_xx, c = dS/dm_xy:
+ *   c = 2 A1 / (B1 B2),  b = -S / B2,  a = 2 mu_y (A2 - A1) / (B1 B2) - 2 mu_x S (1 / B1 - 1 / B2).
+ *
+ * thz_ssim_backward: grad_x[p] (+)= gate g[nc] / (H' W') ((w * a)[p] + 2 x[p] (w * b)[p] + y[p] (w * c)[p]),
+ * * the full separable correlation over the positions whose window covers pixel p, gathered per
+ * pixel (no atomics); g device [NC], the gradient of ssim[nc]; gate = (ssim[nc] > 0) when
+ * nonnegative, else 1; accumulate adds into grad_x.
+ * A null descriptor or pointer and NC, H or W < 1 are THZ_E_ARG; NC > 65535 is THZ_E_UNSUPPORTED.
+ */
+#define THZ_SSIM_MAX_WIN 33
+typedef struct thz_ssim_desc {
+  int NC, H, W;
+  int ws;                          /* taps */
+  float window[THZ_SSIM_MAX_WIN];  /* the first ws entries */
+  double C1, C2;
+  int nonnegative;                 /* nonnegative_ssim */
+  int accumulate;                  /* backward: grad_x += */
+} thz_ssim_desc;
+int thz_ssim_workspace_size(const thz_ssim_desc* d, size_t* bytes);
+int thz_ssim_forward(const thz_ssim_desc* d, const float* x, const float* y, float* ssim, float* cs, float* coef,
+                     void* workspace, size_t bytes, thz_stream_t stream);
+int thz_ssim_backward(const thz_ssim_desc* d, const float* x, const float* y, const float* coef, const float* ssim,
+                      const float* g, float* grad_x, thz_stream_t stream);
+
+/*
  * Batched 1-D FFT along the contiguous axis (the building block of ft2/ift2,
  * utils/Helper_Functions.py:150, without shifts): in/out [rows, n], unnormalised,
  * inverse != 0 for the backward transform.  n <= 16384, any factorisation.
@@ -809,7 +890,8 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * "rsc_slice_acc_adj", "rsc_slice_rows_adj"; the polarization entries: "stokes_fwd", "stokes_bwd",
  * "polarization_ellipse", "stokes64_fwd", "polarization_ellipse64"; the noise entries: "noise_apply",
  * "noise_draws", "signal_scale_part", "signal_scale_finish", "snr_noise_bwd_part", "snr_noise_bwd_finish",
- * "snr_noise_bwd"; ...).
+ * "snr_noise_bwd"; the loss entries: "dice_bce_sums", "dice_bce_finish", "dice_bce_bwd", "ssim_fwd",
+ * "ssim_finish", "ssim_bwd"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

@@ -16,7 +16,7 @@ _ALIASES = ("DataType", "Props", "Components", "LightSource", "utils", "Addons",
 _MODULES = ("DataType.ElectricField", "Props.ASM_Prop", "Props.CZT_Prop", "Props.RSC_Prop",
             "Components.QuantizedDOE", "Components.Thin_Lens", "Components.Aperture",
             "LightSource.Gaussian_beam", "Addons.Field_Resampler", "Addons.Field_Crop", "Addons.Polarization",
-            "Addons.Noise", "utils.Noise",
+            "Addons.Noise", "utils.Noise", "utils.losses",
             "utils.units", "utils.Visualization_Helper", "utils.Helper_Functions",
             "VisTools.directions", "VisTools.calc_loss", "VisTools.visualize")
 

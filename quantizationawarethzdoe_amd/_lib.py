@@ -47,6 +47,8 @@ EXPORTED = [
     "thz_stokes64_forward", "thz_polarization_ellipse64",
     "thz_noise_apply", "thz_noise_draws", "thz_signal_scale_workspace_size", "thz_signal_scale",
     "thz_snr_noise_backward",
+    "thz_dice_bce_sums_workspace_size", "thz_dice_bce_sums", "thz_dice_bce_backward",
+    "thz_ssim_workspace_size", "thz_ssim_forward", "thz_ssim_backward",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -206,6 +208,25 @@ class NoiseDesc(ctypes.Structure):
                 ("rng", ctypes.c_void_p), ("stream", ctypes.c_uint)]
 
 
+class DiceBceDesc(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_longlong), ("M", ctypes.c_longlong),
+                ("p", ctypes.c_float), ("smooth", ctypes.c_float),
+                ("terms", ctypes.c_int), ("bce_grad_elementwise", ctypes.c_int),
+                ("weight", ctypes.c_void_p), ("pos_weight", ctypes.c_void_p)]  # const float* device [N M] or NULL
+
+
+SSIM_MAX_WIN = 33
+
+
+class SsimDesc(ctypes.Structure):
+    _fields_ = [("NC", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("ws", ctypes.c_int),
+                ("window", ctypes.c_float * SSIM_MAX_WIN),
+                ("C1", ctypes.c_double), ("C2", ctypes.c_double),
+                ("nonnegative", ctypes.c_int), ("accumulate", ctypes.c_int)]
+
+
+LOSS_TERM_DICE, LOSS_TERM_BCE = 1, 2
+
 NOISE_GAUSS, NOISE_UNIFORM, NOISE_POISSON, NOISE_POISSON_GAUSS = 0, 1, 2, 3
 NOISE_IN_REAL32, NOISE_IN_FIELD_INTENSITY, NOISE_IN_COMPLEX64 = 0, 1, 2
 DRAW_NORMAL, DRAW_UNIFORM, DRAW_COMPLEX_NORMAL = 0, 1, 2
@@ -306,6 +327,16 @@ def _declare(lib):
     lib.thz_signal_scale.argtypes = [c_void_p, c_ll, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.thz_snr_noise_backward.argtypes = [c_void_p, c_void_p, c_ll, c_int, c_float, c_void_p, c_void_p, c_uint,
                                            c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_dice_bce_sums_workspace_size.argtypes = [ctypes.POINTER(DiceBceDesc), ctypes.POINTER(c_size_t)]
+    lib.thz_dice_bce_sums.argtypes = [ctypes.POINTER(DiceBceDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_size_t, c_void_p]
+    lib.thz_dice_bce_backward.argtypes = [ctypes.POINTER(DiceBceDesc), c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]
+    lib.thz_ssim_workspace_size.argtypes = [ctypes.POINTER(SsimDesc), ctypes.POINTER(c_size_t)]
+    lib.thz_ssim_forward.argtypes = [ctypes.POINTER(SsimDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]
+    lib.thz_ssim_backward.argtypes = [ctypes.POINTER(SsimDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,
