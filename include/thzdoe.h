@@ -774,6 +774,80 @@ int thz_ssim_backward(const thz_ssim_desc* d, const float* x, const float* y, co
                       const float* g, float* grad_x, thz_stream_t stream);
 
 /*
+ * Look-up-table quantizers of a height map (thz_heightmap.hip).  x [n] float32; q [n] float32 = lut[idx];
+ * idx [n] int32.  The L levels (1 .. THZ_MAX_LUT) and the T thresholds travel by value in the descriptor and
+ * are compared in fp32 exactly as given, so q and idx equal torch's bit for bit.
+ *   THZ_LUTQ_BUCKETIZE  nearest_idx / nearest_neighbor_search (utils/Helper_Functions.py:375-398):
+ *       idx = #{j < T : !(thresholds[j] > x)} = torch.bucketize(x, thresholds, right=True) on ascending
+ *       thresholds (a NaN x counts every threshold, as torch does); wrap != 0 then takes idx mod T -- the
+ *       reference's `idx % len(lut_midvals)` (:398), which sends every x at or above the top threshold to
+ *       level 0 (kept: a height map's top level is the phase wrap of level 0).  T <= L - 1 without wrap,
+ *       1 <= T <= L with it, so idx < L.
+ *   THZ_LUTQ_ARGMIN     the notebooks' quantization(input, lut) (experiment_extend_depth_of_focus.ipynb cell
+ *       "def quantization", experiment_dual_plane_hologram.ipynb): idx = argmin_j |x - lut[j]|, the first
+ *       minimum (ties to the lower index, as torch.argmin); a NaN x gives 0.  T is ignored.
+ * One streaming pass, 4 B read and 8 B written per element; 16-byte accesses when x, q and idx are 16-byte
+ * aligned (a last group that crosses n moves element by element), element-width accesses otherwise.
+ *
+ * thz_lut_quantize_backward: grad_in = grad_out f(x, idx) in one pass (16 B per element), the surrogate
+ * gradients of Components/quantization.py:
+ *   THZ_LUTQ_GRAD_IDENTITY  f = 1                                      (NearestNeighborSearch, :70-71)
+ *   THZ_LUTQ_GRAD_POLY      f = nan_to_num(0.5 s (1 - |z|)^(s - 1)) 2  (NearestNeighborPolyGrad, :79-96)
+ *   THZ_LUTQ_GRAD_SIGMOID   f = sigma(s z) (1 - sigma(s z)) 4 s        (NearestNeighborSigmoidGrad, :104-122)
+ * with q = lut[idx], d = sign(x - q) (0 when x == q or x - q is not finite), other = lut[idx + d],
+ * mid = (other + q) / 2, gap = |other - q| + 1e-20, z = 2 (x - mid) / gap; so x == q gives z = 0.  idx + d = -1
+ * reads the last level, as the reference's negative index does; idx + d = L, where the reference's index
+ * raises, reads level 0; a stored idx outside [0, L) is clamped into it.  s: device float [1], read by the
+ * kernel (a captured graph sees each replay's value); NULL for the identity kind.
+ * A null descriptor or pointer, n < 0, a mode or kind outside the lists and T outside the ranges above are
+ * THZ_E_ARG; L outside 1 .. THZ_MAX_LUT is THZ_E_UNSUPPORTED.
+ */
+#define THZ_LUTQ_BUCKETIZE 0
+#define THZ_LUTQ_ARGMIN 1
+#define THZ_LUTQ_GRAD_IDENTITY 0
+#define THZ_LUTQ_GRAD_POLY 1
+#define THZ_LUTQ_GRAD_SIGMOID 2
+typedef struct thz_lut_quantize_desc {
+  long long n;
+  int mode;                       /* THZ_LUTQ_BUCKETIZE / THZ_LUTQ_ARGMIN (forward) */
+  int wrap;                       /* bucketize: idx mod T */
+  int kind;                       /* THZ_LUTQ_GRAD_* (backward) */
+  int L, T;                       /* levels, thresholds */
+  float lut[THZ_MAX_LUT];
+  float thresholds[THZ_MAX_LUT];
+} thz_lut_quantize_desc;
+int thz_lut_quantize_forward(const thz_lut_quantize_desc* d, const float* x, float* q, int* idx, thz_stream_t stream);
+int thz_lut_quantize_backward(const thz_lut_quantize_desc* d, const float* x, const int* idx, const float* grad_out,
+                              const float* s, float* grad_in, thz_stream_t stream);
+
+/*
+ * Total variation of a height map (utils/Helper_Functions.py:40-70) on x [N][H][W] float32 (the caller
+ * flattens the leading dimensions).  center_difference (:56-70):
+ *   dx[i][j] = W / 4 (-x[i][j-1] + 2 x[i][j] - x[i][j+1])  for 1 <= j <= W - 2, else 0
+ *   dy[i][j] = H / 4 (-x[i-1][j] + 2 x[i][j] - x[i+1][j])  for 1 <= i <= H - 2, else 0
+ * and total_variation (:40-54) = mean |dx| + mean |dy| over all N H W elements, borders included.
+ * thz_tv_forward reads x once: a wave owns a tile of 256 columns x 32 rows, a lane four consecutive
+ * columns; it walks down the rows with the previous, current and next row in registers and takes the
+ * columns left and right of its four from the neighbouring lanes (the tile's own edge columns by a
+ * one-element load).  With dx and dy non-NULL it writes both maps (tv, workspace may be NULL); with both
+ * NULL it forms sum |dx| and sum |dy| as fp64 partials per workgroup in the workspace, added in index
+ * order by a finish kernel that writes tv [1] -- no atomics, the same input gives the same bits.
+ *
+ * thz_tv_backward gathers the adjoint stencil per element (no atomics):
+ *   grad[i][j] = W / 4 (2 u[i][j] - u[i][j-1] - u[i][j+1]) + H / 4 (2 v[i][j] - v[i-1][j] - v[i+1][j]),
+ * u, v zero outside the interior columns / rows.  With x non-NULL (total_variation): u = sign(dx) g / (N H W),
+ * v = sign(dy) g / (N H W), g = *grad_loss (device [1]), sign(0) = 0 as torch's abs backward; gdx, gdy NULL.
+ * With x NULL (center_difference): u = gdx, v = gdy, the cotangents of the two maps; grad_loss NULL.
+ * A null pointer and N, H or W < 1 are THZ_E_ARG; H or W above 2^30 and more than 2^31 - 1 workgroups are
+ * THZ_E_UNSUPPORTED; a workspace below thz_tv_workspace_size is THZ_E_WORKSPACE.
+ */
+int thz_tv_workspace_size(long long N, int H, int W, size_t* bytes);
+int thz_tv_forward(const float* x, long long N, int H, int W, float* dx, float* dy, float* tv, void* workspace,
+                   size_t bytes, thz_stream_t stream);
+int thz_tv_backward(const float* x, const float* gdx, const float* gdy, const float* grad_loss, long long N, int H,
+                    int W, float* grad, thz_stream_t stream);
+
+/*
  * Batched 1-D FFT along the contiguous axis (the building block of ft2/ift2,
  * utils/Helper_Functions.py:150, without shifts): in/out [rows, n], unnormalised,
  * inverse != 0 for the backward transform.  n <= 16384, any factorisation.
@@ -891,7 +965,8 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * "polarization_ellipse", "stokes64_fwd", "polarization_ellipse64"; the noise entries: "noise_apply",
  * "noise_draws", "signal_scale_part", "signal_scale_finish", "snr_noise_bwd_part", "snr_noise_bwd_finish",
  * "snr_noise_bwd"; the loss entries: "dice_bce_sums", "dice_bce_finish", "dice_bce_bwd", "ssim_fwd",
- * "ssim_finish", "ssim_bwd"; ...).
+ * "ssim_finish", "ssim_bwd"; the height-map entries: "lut_quantize_fwd", "lut_quantize_bwd", "center_difference",
+ * "tv_fwd", "tv_finish", "tv_bwd", "center_difference_bwd"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

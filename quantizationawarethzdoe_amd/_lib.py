@@ -49,6 +49,8 @@ EXPORTED = [
     "thz_snr_noise_backward",
     "thz_dice_bce_sums_workspace_size", "thz_dice_bce_sums", "thz_dice_bce_backward",
     "thz_ssim_workspace_size", "thz_ssim_forward", "thz_ssim_backward",
+    "thz_lut_quantize_forward", "thz_lut_quantize_backward",
+    "thz_tv_workspace_size", "thz_tv_forward", "thz_tv_backward",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -227,6 +229,9 @@ class SsimDesc(ctypes.Structure):
 
 LOSS_TERM_DICE, LOSS_TERM_BCE = 1, 2
 
+LUTQ_BUCKETIZE, LUTQ_ARGMIN = 0, 1
+LUTQ_GRAD_IDENTITY, LUTQ_GRAD_POLY, LUTQ_GRAD_SIGMOID = 0, 1, 2
+
 NOISE_GAUSS, NOISE_UNIFORM, NOISE_POISSON, NOISE_POISSON_GAUSS = 0, 1, 2, 3
 NOISE_IN_REAL32, NOISE_IN_FIELD_INTENSITY, NOISE_IN_COMPLEX64 = 0, 1, 2
 DRAW_NORMAL, DRAW_UNIFORM, DRAW_COMPLEX_NORMAL = 0, 1, 2
@@ -250,6 +255,13 @@ APERTURE_RECT, APERTURE_CIRC = 1, 2
 
 Q_FP, Q_STE, Q_PSQ, Q_SGV3, Q_NGS, Q_SGV1 = 0, 1, 2, 3, 4, 5
 THZ_MAX_LUT = 16
+
+
+class LutQuantizeDesc(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_longlong), ("mode", ctypes.c_int), ("wrap", ctypes.c_int), ("kind", ctypes.c_int),
+                ("L", ctypes.c_int), ("T", ctypes.c_int),
+                ("lut", ctypes.c_float * THZ_MAX_LUT), ("thresholds", ctypes.c_float * THZ_MAX_LUT)]
+
 
 _lib = None
 _lock = threading.Lock()
@@ -337,6 +349,13 @@ def _declare(lib):
                                      c_void_p, c_size_t, c_void_p]
     lib.thz_ssim_backward.argtypes = [ctypes.POINTER(SsimDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p]
+    lib.thz_lut_quantize_forward.argtypes = [ctypes.POINTER(LutQuantizeDesc), c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.thz_lut_quantize_backward.argtypes = [ctypes.POINTER(LutQuantizeDesc), c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p]
+    lib.thz_tv_workspace_size.argtypes = [c_ll, c_int, c_int, ctypes.POINTER(c_size_t)]
+    lib.thz_tv_forward.argtypes = [c_void_p, c_ll, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                   c_void_p]
+    lib.thz_tv_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, c_void_p, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,

@@ -491,9 +491,10 @@ __device__ __forceinline__ float2 vrs_ez(float2 ex, float2 ey, float x, float y,
 // The lane of a 16-byte streaming kernel (the polarization kernels of thz_optics.hip, the noise
 // kernels of thz_noise.hip): four elements per lane per round of a grid-stride loop over chunks of
 // POL_CHUNK.  WIDE: four consecutive elements moved as 16-byte accesses (the host picks it only when
-// every pointer is 16-byte aligned and n % 4 == 0); otherwise element-width accesses, the lane's
-// elements a workgroup apart (coalesced).  A group that crosses n moves element by element under a
-// bound check in either form.  at(k) is the element index of the lane's k-th value.
+// every pointer is 16-byte aligned; callers that index rows of length m into the arrays also need
+// m % 4 == 0, so that every row starts aligned -- a flat array does not); otherwise element-width
+// accesses, the lane's elements a workgroup apart (coalesced).  A group that crosses n moves element
+// by element under a bound check in either form, which is what serves a flat n with n % 4 != 0.  at(k) is the element index of the lane's k-th value.
 // ---------------------------------------------------------------------------------------------
 constexpr int POL_THREADS = 256;
 constexpr int POL_PX = 4;  // pixels per lane per round
@@ -542,6 +543,25 @@ struct PolLane {
   __device__ __forceinline__ void store(float* __restrict__ a, const float v[POL_PX]) const {
     if (full) {
       *reinterpret_cast<float4*>(a + p0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < POL_PX; ++k)
+        if (at(k) < n) a[at(k)] = v[k];
+    }
+  }
+  // int32 planes (the level indices of thz_heightmap.hip)
+  __device__ __forceinline__ void load(const int* __restrict__ a, int v[POL_PX]) const {
+    if (full) {
+      const int4 f = *reinterpret_cast<const int4*>(a + p0);
+      v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < POL_PX; ++k) v[k] = at(k) < n ? a[at(k)] : 0;
+    }
+  }
+  __device__ __forceinline__ void store(int* __restrict__ a, const int v[POL_PX]) const {
+    if (full) {
+      *reinterpret_cast<int4*>(a + p0) = make_int4(v[0], v[1], v[2], v[3]);
     } else {
 #pragma unroll
       for (int k = 0; k < POL_PX; ++k)

@@ -4,12 +4,68 @@
 on the LDS Stockham FFT kernel (``thz_fft_rows``) along each axis; the shifts are device rolls.
 ``normalize`` (:185-193): divide each batch item by its max **in place**, as the reference does.
 The propagators themselves never call these (they use the shift-free pipeline).
+
+``total_variation`` / ``center_difference`` (:40-70) and the look-up-table helpers ``lut_mid`` /
+``nearest_neighbor_search`` / ``nearest_idx`` (:371-398) run on the kernels of thz_heightmap.hip through
+``optics``; they keep the reference's quirks: the 6-D input of ``total_variation`` is *viewed* as
+[B T P, C, H, W] (a non-contiguous one raises, as ``Tensor.view`` does), ``center_difference`` takes
+exactly four dimensions, and ``nearest_idx`` ends with ``idx % len(lut_midvals)``, which sends every value
+at or above the top threshold to index 0.  ``tt``, ``regular_grid2D`` / ``regular_grid4D``, ``generateGrid`` and
+``set_default_device`` (:25-38, :72-97, :163-182) are plain torch: coordinate grids built once per
+set-up, off the hot path, kept so that the section imports as a block.
 """
 from __future__ import annotations
 
+import copy
+from typing import Union
+
 import torch
 
+from quantizationawarethzdoe_amd import optics as _optics
 from quantizationawarethzdoe_amd import propagation as _prop
+
+
+def set_default_device(device: Union[str, torch.device]):
+    """Make ``device`` torch's default for new tensors (:25-38, without its debug prints)."""
+    if not isinstance(device, torch.device):
+        device = torch.device(device)
+    if device.type == 'cuda':
+        torch.set_default_tensor_type(torch.cuda.FloatTensor)
+        torch.cuda.set_device(device.index)
+    else:
+        torch.set_default_tensor_type(torch.FloatTensor)
+
+
+def total_variation(input: torch.Tensor):
+    """|dx|_1 + |dy|_1 of center_difference, each as a mean over every element (:40-54)."""
+    if input.ndim == 6:
+        B, T, P, C, H, W = input.shape
+        input = input.view(B * T * P, C, H, W)
+    _, _, H, W = input.shape
+    return _optics.total_variation(input)
+
+
+def center_difference(input: torch.Tensor):
+    """dx, dy: the centred second difference scaled by W / 4, H / 4, zero on the border (:56-70)."""
+    _, _, H, W = input.shape
+    return _optics.center_difference(input)
+
+
+def tt(x):
+    return torch.tensor(x)
+
+
+def regular_grid4D(M, N, H, W, range=tt([[-1, 1], [-1, 1], [-1, 1], [-1, 1]]), device=torch.device("cpu")):
+    """Regular 4-D coordinate mesh of M x N x H x W points inside ``range`` (:75-86)."""
+    axes = [torch.linspace(range[i, 0], range[i, 1], n, device=device) for i, n in enumerate((M, N, H, W))]
+    return torch.meshgrid(*axes)
+
+
+def regular_grid2D(H, W, range=tt([[-1, 1], [-1, 1]]), device=torch.device("cpu")):
+    """Regular 2-D coordinate mesh; the x axis (W points) comes first, as in the reference (:88-97)."""
+    x_c = torch.linspace(range[0, 0], range[0, 1], W, device=device)
+    y_c = torch.linspace(range[1, 0], range[1, 1], H, device=device)
+    return torch.meshgrid(x_c, y_c)
 
 
 def _fft2(x, inverse):
@@ -51,6 +107,25 @@ def ft2(input, delta=1, norm='ortho', pad=False):
 
 def ift2(input, delta=1, norm='ortho', pad=False):
     return perform_ft(input=input, delta=delta, norm=norm, pad=pad, flag_ifft=True)
+
+
+def generateGrid(res, deltaX, deltaY, centerGrids=True, centerAroundZero=True, device=None):
+    """x and y coordinate meshes of a res[0] x res[1] grid with the given spacings (:163-182)."""
+    if torch.is_tensor(deltaX):
+        deltaX = copy.deepcopy(deltaX).squeeze().to(device=device)
+    if torch.is_tensor(deltaY):
+        deltaY = copy.deepcopy(deltaY).squeeze().to(device=device)
+
+    def axis(n, delta):
+        if centerGrids and centerAroundZero:
+            c = torch.linspace(-((n - 1) // 2), (n - 1) // 2, n)
+        elif centerGrids:
+            c = torch.linspace(0, n - 1, n) - (n // 2)
+        else:
+            c = torch.linspace(0, n - 1, n)
+        return c.to(device=device) * delta
+
+    return torch.meshgrid(axis(res[0], deltaX), axis(res[1], deltaY))
 
 
 def normalize(x):
@@ -110,6 +185,25 @@ def DOE_xyz_cordinates_Generator(height_map, dxy, new_dxy=0.001, origin='center'
     xyz = np.stack([xc.flatten(), yc.flatten(), z], axis=-1).reshape(-1, 3)
     np.savetxt(f"DOE_xyz_coordinates_{datetime.now().strftime('%Y%m%d-%H%M%S')}.csv", xyz, delimiter=",")
     return xyz
+
+
+# ---- look-up table helpers (:371-398) ------------------------------------------------------------
+def lut_mid(lut):
+    return [(a + b) / 2 for a, b in zip(lut[:-1], lut[1:])]
+
+
+def nearest_neighbor_search(input_val, lut, lut_midvals=None):
+    """(lut[idx], idx) with idx = nearest_idx(input_val, lut_midvals) (:375-387), one kernel pass.  The
+    reference's assert that idx holds no NaN is dropped: an integer tensor holds none, and the check
+    would wait for the device."""
+    len(lut_midvals)  # the reference's TypeError when the thresholds are left out
+    return _optics.lut_quantize(input_val, lut, midvals=lut_midvals, wrap=True, surrogate=None)
+
+
+def nearest_idx(input_val, lut_midvals):
+    """torch.bucketize(input, lut_midvals, right=True) % len(lut_midvals) (:390-398), int64."""
+    levels = [0.0] * len(lut_midvals)  # the index alone: any table of that many levels
+    return _optics.lut_quantize(input_val, levels, midvals=lut_midvals, wrap=True, surrogate=None)[1]
 
 
 # the noise models the reference repeats here (utils/Helper_Functions.py:258-366, the sigma forms)
