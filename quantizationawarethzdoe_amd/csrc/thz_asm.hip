@@ -1162,7 +1162,8 @@ __device__ __forceinline__ void rows_inv_pair_body(const float2* __restrict__ U,
   const TwLds twl = tw_lds_at<PN>(tw_slot2<PN>(lds));
   auto tw_hook = [&]() { tw_store<PN, TT>(tw_slot2<PN>(lds), twf, tid); };
   // the gather of rows_inv_body; row r is even, so (r, r + 1) of a column are one aligned float4
-  // (U's rows are padded to whole tiles: the load stays inside the plane for the one-row tail)
+  // (u_rows rounds U's rows up to whole tiles before it adds its stride pad: row r + 1 of the one-row
+  // tail lies in the tile of row r, so the load stays inside the column's block, short of the pad)
   constexpr int NB0 = PN / pow2_v(PN);
   static_assert(NB0 % CBU == 0, "band offsets must be whole U blocks");
   static_assert(Geo<PN>::T == NB0 && NB0 == PN / 16, "radix-16 first stage, one butterfly per thread");
@@ -1682,7 +1683,7 @@ static void geometry(const thz_asm_desc* d, AsmGeom* g) {
     // 288 GB HBM.  Measured on cfg2 (64 planes, round 2): z_chunk 32 / 64 -> 6830 / 7270 planes/s.
     // The Z-summing adjoint keeps the chunk's input planes in T instead (same cap).
     const double per_z = d->adjoint ? (double)g->BC * g->ncb * CB * g->Hin * sizeof(float2)
-                                    : (double)g->BC * g->ncbu * CBU * g->Hout * sizeof(float2);
+                                    : (double)g->BC * g->ncbu * CBU * u_rows(g->Hout) * sizeof(float2);
     zc = (int)std::max(1.0, std::min(64.0, std::floor((10240.0 * 1024 * 1024) / per_z)));
   }
   g->zc = std::min(zc, d->Z);

@@ -54,7 +54,18 @@ __device__ __forceinline__ size_t blk(int c, int row, int rows) {
 // multiple of URT (u_rows).  Taller tiles give the column pass more of each line (2 x 8: K2 -8 %,
 // 1 x 16: whole lines, K2 -8..-10 %) and cost the row pass more (K3 +33 %, +134 %:
 // profiles/r06_experiments.txt 9), so 4 x 4 stays.
-__host__ __device__ constexpr int u_rows(int rows) { return (rows + URT - 1) / URT * URT; }
+//
+// u_rows is the block stride in rows, on host and device.  Where the stride in bytes (u_rows x CBU x
+// 8) would be a multiple of 4096 -- 2^17 at cfg2, where the row pass gathers 1026 lines with equal
+// address bits 0..16 -- it carries U_PAD_QUADS more row quads, so that block b starts b lines further
+// into those bits (K3 3.80 -> 3.45 ms at cfg2; 33, 34 and 65 quads gave the row
+// pass the same and cost the column pass more, so the smallest).  Whole quads keep every 128-B line and 32-B sector aligned.  Nothing reads
+// or writes the pad rows.  Other strides (the 300- and 500-point sizes) keep the unpadded layout.
+constexpr int U_PAD_QUADS = 1;
+__host__ __device__ constexpr int u_rows(int rows) {
+  const int t = (rows + URT - 1) / URT * URT;
+  return (t * CBU * (int)sizeof(float2)) % 4096 == 0 ? t + U_PAD_QUADS * URT : t;
+}
 __device__ __forceinline__ size_t blk_u(int c, int row, int rows) {
   return ((size_t)(c / CBU) * u_rows(rows) + (row & ~(URT - 1))) * CBU + (c % CBU) * URT + (row & (URT - 1));
 }
