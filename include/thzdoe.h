@@ -66,7 +66,9 @@ typedef void* thz_stream_t; /* hipStream_t */
  * descriptor-free polarization entries thz_stokes_forward, thz_stokes_backward,
  * thz_polarization_ellipse, thz_stokes64_forward and thz_polarization_ellipse64, and the noise
  * entries thz_noise_apply (with its new thz_noise_desc), thz_noise_draws,
- * thz_signal_scale_workspace_size, thz_signal_scale and thz_snr_noise_backward):
+ * thz_signal_scale_workspace_size, thz_signal_scale and thz_snr_noise_backward, and the metrics entries
+ * thz_region_stats_workspace_size, thz_region_stats_forward, thz_region_stats_backward (with their new
+ * thz_region_stats_desc) and thz_line_widths):
  * a caller compares thz_abi_version()
  * with the THZ_ABI_VERSION it was compiled against before its first call, since a shorter
  * struct from an older header would make the library read past it.  Descriptors are plain C
@@ -848,6 +850,69 @@ int thz_tv_backward(const float* x, const float* gdx, const float* gdy, const fl
                     int W, float* grad, thz_stream_t stream);
 
 /*
+ * Focal-spot figures of merit (thz_metrics.hip; quantizationawarethzdoe_amd/utils/metrics.py -- the
+ * reference's utils/metrics.py is an empty placeholder, these follow its notebooks' conventions).
+ *
+ * thz_region_stats_forward: x is N contiguous planes of H x W elements of `dtype`: a field (complex64 /
+ * complex128, interleaved re, im; I = re^2 + im^2 formed in fp64 with separate multiplies and one add) or an
+ * intensity (float32 / float64, I = x).  regions: K (0 .. THZ_MAX_REGIONS) entries {kind, cr, cc, a, b} in
+ * pixel units (row i, column j), a host table copied into the launch or, with regions_on_device, a device
+ * table read by the kernels (then a kind other than THZ_REGION_CIRC is read as THZ_REGION_RECT):
+ *   THZ_REGION_CIRC  (i - cr)^2 + (j - cc)^2 <= a^2        THZ_REGION_RECT  |i - cr| <= a and |j - cc| <= b
+ * evaluated in fp64 from the fp32 values.  Region index K is the whole plane.
+ * out: fp64 [N, K + 1, 8] = S0 = sum I, Sr = sum I i, Sc = sum I j, Srr = sum I i^2, Scc = sum I j^2,
+ * peak = max I, argmax (the lowest flat index i W + j that attains it), count (pixels inside).  A region with
+ * no pixel in the plane gives zeros, peak = 0 and argmax = -1; a NaN never wins the peak.
+ * One pass: an element is read once for all regions (a 256 x 32 tile visits only the regions whose bounding
+ * box meets it); fp64 sums per workgroup in a fixed order into the workspace, merged per plane in tile order by
+ * a second launch -- no atomics, the same input gives the same bits; no host read.  16-byte loads when x is
+ * 16-byte aligned and a row's bytes are a multiple of 16, element-width loads otherwise (same results).
+ *
+ * thz_region_stats_backward: G fp64 [N, K + 1, 5], the cotangents of the five sums; one pass writes
+ *   grad_I(n, i, j) = sum over the regions k holding (i, j) of G0 + G1 i + G2 j + G3 i^2 + G4 j^2
+ * as grad_I (intensities; x may be NULL) or 2 grad_I x (fields, the convention of thz_stokes_backward) in
+ * x's dtype.  peak, argmax and count carry no gradient.
+ *
+ * thz_line_widths: v is L contiguous lines of W samples (THZ_METRICS_F32 / THZ_METRICS_F64), 0 < level < 1.
+ * out: fp64 [L, 5] = peak, argmax (lowest index), xl, xr, xr - xl, the nearest crossings of t = level peak on
+ * either side of the peak, in samples: with j the largest index below argmax with v[j] < t,
+ * xl = j + (t - v[j]) / (v[j + 1] - v[j]) in fp64; xr the mirror image, j the smallest index above argmax with
+ * v[j] < t, xr = j - (t - v[j]) / (v[j - 1] - v[j]).  A side with no such sample gives NaN there and for the
+ * width.  A wave per line up to 1024 samples, a workgroup per line beyond.
+ *
+ * A null descriptor / pointer, negative N, H, W or L, W < 1 (lines), K outside 0 .. THZ_MAX_REGIONS, an unknown
+ * dtype or host region kind, a level outside (0, 1) and a misaligned array or workspace are THZ_E_ARG; H or W
+ * above 2^30 and more than 2^31 - 1 workgroups are THZ_E_UNSUPPORTED; a workspace below
+ * thz_region_stats_workspace_size is THZ_E_WORKSPACE.
+ */
+#define THZ_MAX_REGIONS 16
+#define THZ_REGION_CIRC 0
+#define THZ_REGION_RECT 1
+#define THZ_METRICS_C64 0
+#define THZ_METRICS_C128 1
+#define THZ_METRICS_F32 2
+#define THZ_METRICS_F64 3
+typedef struct thz_region {
+  int kind;          /* THZ_REGION_* */
+  float cr, cc;      /* centre: row, column */
+  float a, b;        /* circ: radius a (b unused); rect: half-height a, half-width b */
+} thz_region;
+typedef struct thz_region_stats_desc {
+  long long N;               /* planes */
+  int H, W;
+  int dtype;                 /* THZ_METRICS_* */
+  int K;                     /* 0 .. THZ_MAX_REGIONS */
+  const thz_region* regions; /* [K]; NULL when K == 0 */
+  int regions_on_device;     /* 0: host table, 1: device table */
+} thz_region_stats_desc;
+int thz_region_stats_workspace_size(const thz_region_stats_desc* d, size_t* bytes);
+int thz_region_stats_forward(const thz_region_stats_desc* d, const void* x, double* out, void* workspace, size_t bytes,
+                             thz_stream_t stream);
+int thz_region_stats_backward(const thz_region_stats_desc* d, const void* x, const double* G, void* grad,
+                              thz_stream_t stream);
+int thz_line_widths(const void* v, int dtype, long long L, int W, double level, double* out, thz_stream_t stream);
+
+/*
  * Batched 1-D FFT along the contiguous axis (the building block of ft2/ift2,
  * utils/Helper_Functions.py:150, without shifts): in/out [rows, n], unnormalised,
  * inverse != 0 for the backward transform.  n <= 16384, any factorisation.
@@ -966,7 +1031,8 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * "noise_draws", "signal_scale_part", "signal_scale_finish", "snr_noise_bwd_part", "snr_noise_bwd_finish",
  * "snr_noise_bwd"; the loss entries: "dice_bce_sums", "dice_bce_finish", "dice_bce_bwd", "ssim_fwd",
  * "ssim_finish", "ssim_bwd"; the height-map entries: "lut_quantize_fwd", "lut_quantize_bwd", "center_difference",
- * "tv_fwd", "tv_finish", "tv_bwd", "center_difference_bwd"; ...).
+ * "tv_fwd", "tv_finish", "tv_bwd", "center_difference_bwd"; the metrics entries: "region_stats_fwd",
+ * "region_stats_finish", "region_stats_bwd", "line_widths"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

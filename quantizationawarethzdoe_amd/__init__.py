@@ -17,7 +17,7 @@ _MODULES = ("DataType.ElectricField", "Props.ASM_Prop", "Props.CZT_Prop", "Props
             "Components.QuantizedDOE", "Components.Thin_Lens", "Components.Aperture",
             "Components.quantization", "Components.discrete_doe",
             "LightSource.Gaussian_beam", "Addons.Field_Resampler", "Addons.Field_Crop", "Addons.Polarization",
-            "Addons.Noise", "utils.Noise", "utils.losses",
+            "Addons.Noise", "utils.Noise", "utils.losses", "utils.metrics",
             "utils.units", "utils.Visualization_Helper", "utils.Helper_Functions",
             "VisTools.directions", "VisTools.calc_loss", "VisTools.visualize")
 

@@ -51,6 +51,7 @@ EXPORTED = [
     "thz_ssim_workspace_size", "thz_ssim_forward", "thz_ssim_backward",
     "thz_lut_quantize_forward", "thz_lut_quantize_backward",
     "thz_tv_workspace_size", "thz_tv_forward", "thz_tv_backward",
+    "thz_region_stats_workspace_size", "thz_region_stats_forward", "thz_region_stats_backward", "thz_line_widths",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -263,6 +264,22 @@ class LutQuantizeDesc(ctypes.Structure):
                 ("lut", ctypes.c_float * THZ_MAX_LUT), ("thresholds", ctypes.c_float * THZ_MAX_LUT)]
 
 
+THZ_MAX_REGIONS = 16
+REGION_CIRC, REGION_RECT = 0, 1
+METRICS_C64, METRICS_C128, METRICS_F32, METRICS_F64 = 0, 1, 2, 3
+
+
+class Region(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("cr", ctypes.c_float), ("cc", ctypes.c_float),
+                ("a", ctypes.c_float), ("b", ctypes.c_float)]
+
+
+class RegionStatsDesc(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_longlong), ("H", ctypes.c_int), ("W", ctypes.c_int), ("dtype", ctypes.c_int),
+                ("K", ctypes.c_int), ("regions", ctypes.c_void_p),  # const thz_region* [K], host or device
+                ("regions_on_device", ctypes.c_int)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -356,6 +373,11 @@ def _declare(lib):
     lib.thz_tv_forward.argtypes = [c_void_p, c_ll, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                    c_void_p]
     lib.thz_tv_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, c_void_p, c_void_p]
+    lib.thz_region_stats_workspace_size.argtypes = [ctypes.POINTER(RegionStatsDesc), ctypes.POINTER(c_size_t)]
+    lib.thz_region_stats_forward.argtypes = [ctypes.POINTER(RegionStatsDesc), c_void_p, c_void_p, c_void_p, c_size_t,
+                                             c_void_p]
+    lib.thz_region_stats_backward.argtypes = [ctypes.POINTER(RegionStatsDesc), c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.thz_line_widths.argtypes = [c_void_p, c_int, c_ll, c_int, ctypes.c_double, c_void_p, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,
