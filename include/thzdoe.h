@@ -913,6 +913,80 @@ int thz_region_stats_backward(const thz_region_stats_desc* d, const void* x, con
 int thz_line_widths(const void* v, int dtype, long long L, int W, double level, double* out, thz_stream_t stream);
 
 /*
+ * The projections of the iterative Fourier-transform algorithm (thz_ifta.hip; quantizationawarethzdoe_amd/
+ * ifta.py -- the reference has no such designer): between the fused DOE -> ASM forward and the Z-summing ASM
+ * adjoint, one iteration imposes the target amplitude on the planes and the level table on the height map.
+ * U is N contiguous planes of H x W complex64 (interleaved re, im).  T is the target amplitude, float32, one
+ * plane [H, W] for every plane of U (target_planes = 1) or [N, H, W] (target_planes = N), non-negative.  M is
+ * the signal window, uint8 [H, W], non-zero inside; NULL: every pixel.  |U| = sqrt(re^2 + im^2) in fp64.
+ *
+ * thz_ifta_target_stats: one pass that reads U, T and M once.  out: fp64 [N, 6] =
+ *   S_all = sum |U|^2, S_in = sum_M |U|^2, S_TU = sum_M T |U|, S_TT = sum_M T^2,
+ *   s = S_TU / S_TT (0 when S_TT = 0), eff = S_in / S_all (0 when S_all = 0);
+ * s is the least-squares scale of s T against |U| over M.  fp64 sums per workgroup (4096 pixels) in a fixed
+ * order into the workspace, added per plane in index order by a second launch -- no atomics, the same input
+ * gives the same bits; no host read.  out is any 8-byte aligned device address (a row of a history array).
+ *
+ * thz_ifta_target_project: out [N, H, W] complex64; scale: device fp64 [N], read by the kernel.
+ *   inside M:   a' = max(0, alpha scale[n] T + (1 - alpha) |U|), out = a' U / |U|; where |U| = 0, out = a'
+ *   outside M:  out = beta U
+ * alpha = 1 is Gerchberg-Saxton, 1 < alpha <= 2 the over-compensated (adaptive-additive) form; beta = 1 leaves
+ * the amplitude outside the window free, beta = 0 suppresses it.  Each pixel is formed in fp64 and rounded to
+ * float32 once.  out == U (in place) is legal; any other overlap is not.
+ * Both read and write 16 bytes per access when U, T and out are 16-byte aligned, M is 4-byte aligned and, with
+ * more than one plane of U or T, H W is a multiple of 4; a last group that crosses the plane's end and every
+ * other case move element by element (same results).  12 - 13 B read per pixel (stats), 13 B read and 8 B
+ * written (project).
+ *
+ * thz_ifta_doe_project: the DOE has hs x ws cells of r_h x r_w field pixels each, H = r_h hs and W = r_w ws
+ * (for these the nearest upsampling of the modulate kernels is block replication).  U [N, H, W] is the
+ * back-propagated field; A the incident field, complex64 [H, W] (incident_planes = 1) or [N, H, W]
+ * (incident_planes = N), or NULL with incident_planes = 0 for A = 1.  Per cell
+ *   g = sum over the cell of U conj(A): products and sum in fp64, the cell's pixels in row-major order (the
+ *       adjoint of the nearest upsampling);  phi = atan2(Im g, Re g), 0 for g = 0;
+ *   the transmission phase of a height h is -kappa (h + base plane), kappa = 2 pi / lambda (sqrt(eps) - 1)
+ *   formed in fp32 as the modulate kernels form it, so
+ *   h_c = ((-phi) / kappa - base plane) mod h_max,  h_max = 2 pi / kappa;
+ *   the nearest level on the circle of circumference h_max, the lowest index on a tie; d the cyclic distance
+ *   to it and G half the gap to its neighbour on h_c's side (G = h_max / 2 for a single level);
+ *   the cell takes the level when d <= q G or q >= 1, and keeps h_c otherwise.
+ * q: device float [1], read by the kernel (a captured graph sees each replay's value); q = 0 leaves the map
+ * continuous, q = 1 snaps every cell.  h: float32 [N, hs, ws], lut[idx] bit for bit where snapped; idx: int32,
+ * the level or -1.  lut: L (1 .. THZ_MAX_LUT) levels ascending in [0, h_max), by value.  The loss tangent takes
+ * no part: the projection fits the phase of the transmission alone, its amplitude exp(-k/2 (h + base) tand
+ * sqrt(eps)) is neither compensated nor used as a weight.  8 - 16 B read per pixel, 8 B written per cell.
+ *
+ * All three are capturable and check their arguments before any device call: a null descriptor or pointer, a
+ * misaligned array, a negative size, target_planes outside {1, N}, incident_planes outside {0, 1, N}, L outside
+ * 1 .. THZ_MAX_LUT, a table that does not ascend or leaves [0, h_max), wavelength <= 0 or epsilon <= 1, alpha
+ * outside (0, 2] and beta outside [0, 1] are THZ_E_ARG; a field that is not a whole number of pixels per cell
+ * and more than 2^31 - 1 workgroups are THZ_E_UNSUPPORTED; a workspace below
+ * thz_ifta_target_stats_workspace_size is THZ_E_WORKSPACE.
+ */
+typedef struct thz_ifta_desc {
+  long long N;               /* planes */
+  int H, W;
+  long long target_planes;   /* 1: T [H, W]; N: T [N, H, W] */
+  double alpha, beta;        /* thz_ifta_target_project only */
+} thz_ifta_desc;
+typedef struct thz_ifta_doe_desc {
+  long long N;               /* fields, one height map each */
+  int H, W;
+  int hs, ws;                /* cells */
+  long long incident_planes; /* 0: A = 1; 1: A [H, W]; N: A [N, H, W] */
+  float wavelength, epsilon;
+  int L;                     /* 1 .. THZ_MAX_LUT */
+  float lut[THZ_MAX_LUT];
+} thz_ifta_doe_desc;
+int thz_ifta_target_stats_workspace_size(const thz_ifta_desc* d, size_t* bytes);
+int thz_ifta_target_stats(const thz_ifta_desc* d, const void* U, const float* T, const unsigned char* M, double* out,
+                          void* workspace, size_t bytes, thz_stream_t stream);
+int thz_ifta_target_project(const thz_ifta_desc* d, const void* U, const float* T, const unsigned char* M,
+                            const double* scale, void* out, thz_stream_t stream);
+int thz_ifta_doe_project(const thz_ifta_doe_desc* d, const void* U, const void* A, const float* q, float* h, int* idx,
+                         thz_stream_t stream);
+
+/*
  * Batched 1-D FFT along the contiguous axis (the building block of ft2/ift2,
  * utils/Helper_Functions.py:150, without shifts): in/out [rows, n], unnormalised,
  * inverse != 0 for the backward transform.  n <= 16384, any factorisation.

@@ -33,6 +33,7 @@ def install_reference_aliases():
             importlib.import_module(f"{__name__}.{sub}")
         except ModuleNotFoundError:
             pass
+    sys.modules["ifta"] = importlib.import_module(f"{__name__}.ifta")  # a module of this port alone
     for name in _ALIASES:
         mod = importlib.import_module(f"{__name__}.{name}")
         sys.modules[name] = mod

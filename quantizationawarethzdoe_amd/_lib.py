@@ -52,6 +52,7 @@ EXPORTED = [
     "thz_lut_quantize_forward", "thz_lut_quantize_backward",
     "thz_tv_workspace_size", "thz_tv_forward", "thz_tv_backward",
     "thz_region_stats_workspace_size", "thz_region_stats_forward", "thz_region_stats_backward", "thz_line_widths",
+    "thz_ifta_target_stats_workspace_size", "thz_ifta_target_stats", "thz_ifta_target_project", "thz_ifta_doe_project",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -280,6 +281,20 @@ class RegionStatsDesc(ctypes.Structure):
                 ("regions_on_device", ctypes.c_int)]
 
 
+class IftaDesc(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_longlong), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("target_planes", ctypes.c_longlong),  # 1: T [H, W]; N: T [N, H, W]
+                ("alpha", ctypes.c_double), ("beta", ctypes.c_double)]
+
+
+class IftaDoeDesc(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_longlong), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("hs", ctypes.c_int), ("ws", ctypes.c_int),
+                ("incident_planes", ctypes.c_longlong),  # 0: none; 1: A [H, W]; N: A [N, H, W]
+                ("wavelength", ctypes.c_float), ("epsilon", ctypes.c_float),
+                ("L", ctypes.c_int), ("lut", ctypes.c_float * THZ_MAX_LUT)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -378,6 +393,13 @@ def _declare(lib):
                                              c_void_p]
     lib.thz_region_stats_backward.argtypes = [ctypes.POINTER(RegionStatsDesc), c_void_p, c_void_p, c_void_p, c_void_p]
     lib.thz_line_widths.argtypes = [c_void_p, c_int, c_ll, c_int, ctypes.c_double, c_void_p, c_void_p]
+    lib.thz_ifta_target_stats_workspace_size.argtypes = [ctypes.POINTER(IftaDesc), ctypes.POINTER(c_size_t)]
+    lib.thz_ifta_target_stats.argtypes = [ctypes.POINTER(IftaDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_size_t, c_void_p]
+    lib.thz_ifta_target_project.argtypes = [ctypes.POINTER(IftaDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]
+    lib.thz_ifta_doe_project.argtypes = [ctypes.POINTER(IftaDoeDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,

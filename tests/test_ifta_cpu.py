@@ -1,0 +1,205 @@
+"""tests/ifta_ref.py pinned on closed forms and brute force, and the host side of the IFTA entries (the ABI, the
+argument checks that come before any device call, the Python argument errors).  No GPU."""
+import ctypes
+import math
+
+import pytest
+import torch
+
+from quantizationawarethzdoe_amd import _lib, optics
+from tests import ifta_ref as ir
+
+LAM, EPS = 2.998e8 / 300e9, 2.66
+HM = ir.h_max(LAM, EPS)
+
+
+def _field(N, H, W, seed, dtype=torch.complex128):
+    g = torch.Generator().manual_seed(seed)
+    rd = torch.float64 if dtype == torch.complex128 else torch.float32
+    return torch.complex(torch.randn(N, H, W, generator=g, dtype=rd), torch.randn(N, H, W, generator=g, dtype=rd))
+
+
+def _disc(H, W):
+    i, j = torch.arange(H)[:, None], torch.arange(W)[None, :]
+    return (i - 0.45 * H) ** 2 + (j - 0.55 * W) ** 2 <= (0.35 * min(H, W)) ** 2
+
+
+def test_scale_minimises_the_amplitude_misfit():
+    U, M = _field(2, 23, 31, 1), _disc(23, 31)
+    T = torch.rand(23, 31, generator=torch.Generator().manual_seed(2), dtype=torch.float64)
+    st = ir.target_stats(U, T, M)
+    a = ir.amplitude(U)
+    for n in range(2):
+        s = float(st[n, 4])
+        cost = lambda v: float((((v * T - a[n]) ** 2) * M).sum())
+        scan = [s * (1 + k * 1e-3) for k in range(-50, 51)]
+        assert min(scan, key=cost) == s
+        assert cost(s) <= min(cost(s * 0.99), cost(s * 1.01))
+        assert float(st[n, 5]) == float(st[n, 1] / st[n, 0]) and 0 < float(st[n, 5]) < 1
+    zero = ir.target_stats(U, T, torch.zeros(23, 31, dtype=torch.bool))
+    assert zero[:, 1:].abs().max() == 0 and not torch.isnan(zero).any()
+
+
+def test_gerchberg_saxton_projection_is_idempotent():
+    U, M = _field(2, 23, 31, 3), _disc(23, 31)
+    U[0, 10, 17] = 0  # inside the window: takes the amplitude itself
+    T = torch.rand(2, 23, 31, generator=torch.Generator().manual_seed(4), dtype=torch.float64)
+    s = ir.target_stats(U, T, M)[:, 4]
+    P = ir.target_project(U, T, s, M, alpha=1.0, beta=1.0)
+    assert torch.allclose(ir.amplitude(P)[:, M], (s[:, None, None] * T)[:, M], rtol=1e-14, atol=0)
+    assert torch.equal(P[:, ~M], U[:, ~M])
+    assert M[10, 17] and P[0, 10, 17] == s[0] * T[0, 10, 17]
+    P2 = ir.target_project(P, T, s, M, alpha=1.0, beta=1.0)
+    assert (P2 - P).abs().max() <= 1e-14 * P.abs().max()
+    assert ir.target_project(U, T, s, M, alpha=1.0, beta=0.0)[:, ~M].abs().max() == 0
+    over = ir.target_project(U, T, s, M, alpha=2.0, beta=1.0)  # the amplitude is clamped at zero
+    want = torch.clamp(2 * s[:, None, None] * T - ir.amplitude(U), min=0)
+    assert torch.allclose(ir.amplitude(over)[:, M], want[:, M], rtol=1e-13, atol=1e-15)
+
+
+@pytest.mark.parametrize("lut", [[0.0], [0.1e-3, 0.9e-3], [0.0, 0.4e-3, 0.8e-3, 1.2e-3], [0.05e-3, 0.2e-3, 0.9e-3, 1.5e-3],
+                                 [HM * i / 10 for i in range(10)]])
+def test_cyclic_partial_snap_equals_brute_force(lut):
+    g = torch.Generator().manual_seed(len(lut))
+    hc = torch.rand(400, generator=g, dtype=torch.float64) * HM
+    hc[:4] = torch.tensor([0.0, HM * (1 - 1e-12), lut[0], lut[-1]], dtype=torch.float64)
+    for q in (0.0, 0.25, 0.5, 0.9, 1.0):
+        h, idx, d, G = ir.snap(hc, lut, HM, q)
+        for k in range(hc.numel()):
+            hb, ib = ir.snap_brute(float(hc[k]), lut, HM, q)
+            assert (float(h[k]), int(idx[k])) == (hb, ib), (q, k, float(hc[k]))
+        assert (d <= G * (1 + 1e-12)).all()
+    h0, i0, d, _ = ir.snap(hc, lut, HM, 0.0)
+    assert torch.equal(h0, hc) and ((i0 == -1) | (d == 0)).all()
+    h1, i1, _, _ = ir.snap(hc, lut, HM, 1.0)
+    assert (i1 >= 0).all() and torch.equal(h1, torch.tensor(lut, dtype=torch.float64)[i1])
+
+
+@pytest.mark.parametrize("hs,ws,rh,rw", [(5, 7, 1, 1), (5, 7, 3, 2), (4, 4, 8, 8)])
+def test_block_sum_is_the_transpose_of_nearest_upsampling(hs, ws, rh, rw):
+    H, W = hs * rh, ws * rw
+    U = _field(2, H, W, 5)
+    A = _field(1, H, W, 6)[0]
+    g, terms = ir.cell_sums(U, A, (hs, ws))
+    x = torch.randn(2, hs, ws, generator=torch.Generator().manual_seed(7), dtype=torch.float64)
+    up = torch.nn.functional.interpolate(x[:, None], size=[H, W], mode="nearest")[:, 0]
+    lhs = (up * (U * A.conj())).sum()
+    rhs = (x * g).sum()
+    assert abs(lhs - rhs) <= 1e-12 * terms.sum()
+    # the height whose transmission has the phase of g: the oracle's own transmission
+    from oracle import thz_oracle as orc
+    hc = ir.continuous_height(g, LAM, EPS)
+    t = orc.doe_transmission(hc[0], torch.tensor([float(torch.tensor(LAM, dtype=torch.float32))], dtype=torch.float64),
+                             EPS, 0.0)[0]
+    # kappa is the layers' float32 factor, the oracle's is float64: 2^-24 of a phase of kappa (h + base) < 20 rad
+    assert (torch.angle(t * g[0].conj())).abs().max() < 20 * 2.0 ** -23
+    assert (hc >= 0).all() and (hc < HM).all()
+
+
+def test_adjoint_is_the_adjoint_of_the_oracle_asm():
+    x = _field(1, 12, 10, 8).reshape(1, 1, 12, 10)
+    y = _field(2, 12, 10, 9).reshape(2, 1, 1, 12, 10)
+    zs = [0.05, 0.08]
+    Ax = ir.asm_planes(x, LAM, 1e-3, zs, 2)
+    Ay = ir.asm_adjoint(y, LAM, 1e-3, zs, 2)
+    lhs, rhs = (Ax.conj() * y).sum(), (x.conj() * Ay).sum()
+    assert abs(lhs - rhs) <= 1e-12 * abs(lhs)
+
+
+def test_abi():
+    for name in ("thz_ifta_target_stats_workspace_size", "thz_ifta_target_stats", "thz_ifta_target_project",
+                 "thz_ifta_doe_project"):
+        assert name in _lib.EXPORTED and hasattr(_lib.lib(), name)
+    assert _lib.lib().thz_abi_version() == 9
+    import quantizationawarethzdoe_amd as pkg
+    from quantizationawarethzdoe_amd import ifta
+    pkg.install_reference_aliases()
+    import ifta as aliased
+    assert aliased is ifta and callable(ifta.IFTA)
+    qs = ifta.default_q_schedule(10)
+    assert qs[0] == 0.0 and qs[7:] == [1.0, 1.0, 1.0] and qs == sorted(qs)
+    assert ifta.default_q_schedule(1) == [1.0]
+    assert math.isclose(ir.kappa(LAM, EPS), __import__("quantizationawarethzdoe_amd.doe", fromlist=["x"]).phase_scale(LAM, EPS))
+
+
+def _doe_desc(**kw):
+    args = dict(N=1, H=8, W=8, hs=4, ws=4, incident_planes=0, wavelength=LAM, epsilon=EPS, L=2)
+    lut = kw.pop("lut", [0.0, 0.5e-3])
+    args.update(kw)
+    d = _lib.IftaDoeDesc(**args)
+    for i, v in enumerate(lut):
+        d.lut[i] = v
+    return d
+
+
+def test_argument_errors_reach_no_launch():
+    """Every documented code from the loaded library with no GPU: the checks come before any device call."""
+    h, err = _lib.lib(), lambda: _lib.lib().thz_last_error()
+    n = ctypes.c_size_t(0)
+    p, odd = ctypes.c_void_p(4096), ctypes.c_void_p(4098)  # never dereferenced
+    D = lambda **kw: _lib.IftaDesc(**{**dict(N=2, H=130, W=1030, target_planes=1, alpha=1.0, beta=1.0), **kw})
+    stats = lambda d, U=p, T=p, M=None, out=p, ws=p, b=1 << 20: h.thz_ifta_target_stats(ctypes.byref(d), U, T, M, out, ws, b, None)
+    proj = lambda d, U=p, T=p, M=None, s=p, out=p: h.thz_ifta_target_project(ctypes.byref(d), U, T, M, s, out, None)
+    doe = lambda d, U=p, A=None, q=p, hh=p, idx=p: h.thz_ifta_doe_project(ctypes.byref(d), U, A, q, hh, idx, None)
+    d = D()
+    assert h.thz_ifta_target_stats_workspace_size(ctypes.byref(d), ctypes.byref(n)) == _lib.THZ_OK
+    assert n.value == (2 * 33 * 4 * 8 + 255) // 256 * 256  # 33 chunks of 4096 pixels per plane, four sums each
+    assert h.thz_ifta_target_stats_workspace_size(None, ctypes.byref(n)) == _lib.THZ_E_ARG
+    assert h.thz_ifta_target_stats_workspace_size(ctypes.byref(d), None) == _lib.THZ_E_ARG
+    for bad in (dict(N=-1), dict(H=-1), dict(W=-3)):
+        assert stats(D(**bad)) == _lib.THZ_E_ARG and b"shape" in err()
+        assert proj(D(**bad)) == _lib.THZ_E_ARG
+    assert stats(D(target_planes=3)) == _lib.THZ_E_ARG and b"target planes" in err()
+    assert stats(d, U=None) == _lib.THZ_E_ARG and stats(d, T=None) == _lib.THZ_E_ARG and stats(d, out=None) == _lib.THZ_E_ARG
+    assert stats(d, U=odd) == _lib.THZ_E_ARG and b"misaligned" in err()
+    assert stats(d, out=ctypes.c_void_p(4100)) == _lib.THZ_E_ARG
+    assert stats(d, ws=ctypes.c_void_p(4100)) == _lib.THZ_E_ARG and b"workspace misaligned" in err()
+    assert stats(d, b=n.value - 256) == _lib.THZ_E_WORKSPACE
+    assert stats(d, ws=None, b=0) == _lib.THZ_E_WORKSPACE
+    assert stats(D(N=1 << 31, H=1, W=1)) == _lib.THZ_E_UNSUPPORTED and b"grid" in err()
+    assert stats(D(N=1 << 20, H=4096, W=4096, target_planes=1)) == _lib.THZ_E_UNSUPPORTED
+    for a in (0.0, -1.0, 2.5, math.nan):
+        assert proj(D(alpha=a)) == _lib.THZ_E_ARG and b"alpha" in err()
+    for b in (-0.1, 1.5, math.nan):
+        assert proj(D(beta=b)) == _lib.THZ_E_ARG and b"beta" in err()
+    assert proj(d, s=None) == _lib.THZ_E_ARG and proj(d, out=None) == _lib.THZ_E_ARG and proj(d, T=odd) == _lib.THZ_E_ARG
+    assert proj(d, s=ctypes.c_void_p(4100)) == _lib.THZ_E_ARG and b"scale" in err()
+    assert proj(D(N=1 << 31, H=1, W=1)) == _lib.THZ_E_UNSUPPORTED
+
+    assert h.thz_ifta_doe_project(None, p, None, p, p, p, None) == _lib.THZ_E_ARG
+    for bad in (dict(N=-1), dict(H=-8), dict(hs=-1), dict(ws=-4)):
+        assert doe(_doe_desc(**bad)) == _lib.THZ_E_ARG and b"shape" in err()
+    for L in (0, 17, -2):
+        assert doe(_doe_desc(L=L)) == _lib.THZ_E_ARG and b"levels" in err()
+    assert doe(_doe_desc(lut=[0.5e-3, 0.2e-3])) == _lib.THZ_E_ARG and b"ascending" in err()
+    assert doe(_doe_desc(lut=[0.2e-3, 0.2e-3])) == _lib.THZ_E_ARG and b"ascending" in err()
+    assert doe(_doe_desc(lut=[-1e-4, 0.2e-3])) == _lib.THZ_E_ARG and b"h_max" in err()
+    assert doe(_doe_desc(lut=[0.0, HM * 1.001])) == _lib.THZ_E_ARG and b"h_max" in err()
+    assert doe(_doe_desc(wavelength=0.0)) == _lib.THZ_E_ARG and doe(_doe_desc(epsilon=1.0)) == _lib.THZ_E_ARG
+    assert doe(_doe_desc(incident_planes=3)) == _lib.THZ_E_ARG and b"incident" in err()
+    assert doe(_doe_desc(incident_planes=1)) == _lib.THZ_E_ARG and b"null" in err()  # A missing
+    assert doe(_doe_desc(), U=None) == _lib.THZ_E_ARG and doe(_doe_desc(), q=None) == _lib.THZ_E_ARG
+    assert doe(_doe_desc(), hh=None) == _lib.THZ_E_ARG and doe(_doe_desc(), idx=None) == _lib.THZ_E_ARG
+    assert doe(_doe_desc(), U=odd) == _lib.THZ_E_ARG and b"misaligned" in err()
+    for bad in (dict(hs=3), dict(ws=5), dict(hs=16), dict(H=0)):
+        assert doe(_doe_desc(**bad)) == _lib.THZ_E_UNSUPPORTED and b"whole number" in err()
+    assert doe(_doe_desc(N=1 << 31, H=1, W=1, hs=1, ws=1)) == _lib.THZ_E_UNSUPPORTED and b"grid" in err()
+    assert doe(_doe_desc(N=0)) == _lib.THZ_OK  # nothing to do, nothing launched
+
+
+def test_python_argument_errors_before_any_launch():
+    U = torch.zeros(2, 8, 8, dtype=torch.complex64)
+    with pytest.raises(RuntimeError, match="ROCm device"):
+        optics.ifta_target_stats(U, torch.zeros(8, 8))
+    with pytest.raises(RuntimeError, match="ROCm device"):
+        optics.ifta_doe_project(U, (4, 4), LAM, EPS, [0.0])
+    with pytest.raises(ValueError, match="alpha"):
+        optics.ifta_target_project(U, torch.zeros(8, 8), torch.zeros(2, dtype=torch.float64), alpha=0.0)
+    with pytest.raises(ValueError, match="beta"):
+        optics.ifta_target_project(U, torch.zeros(8, 8), torch.zeros(2, dtype=torch.float64), beta=2.0)
+    with pytest.raises(ValueError, match="whole number"):
+        optics._ifta_doe_desc(1, 8, 8, (3, 4), LAM, EPS, (0.0,), 0)
+    with pytest.raises(ValueError, match="17 levels"):
+        optics._ifta_doe_desc(1, 8, 8, (4, 4), LAM, EPS, tuple(1e-5 * i for i in range(17)), 0)
+    d = optics._ifta_doe_desc(2, 8, 6, (4, 3), LAM, EPS, (0.0, 1e-4), 2)
+    assert (d.hs, d.ws, d.L, d.incident_planes) == (4, 3, 2, 2) and d.lut[1] == pytest.approx(1e-4)
