@@ -418,6 +418,38 @@ int thz_asm_forward_modulated(const thz_asm_desc* d, const thz_doe_desc* m, cons
                               size_t workspace_bytes, thz_stream_t stream);
 
 /*
+ * Thick-element DOE: split-step (multi-slice) propagation through the relief.  The reference has no
+ * counterpart (its thin screen leaves the field in the plane it entered); a slab's screen is
+ * DOELayer.modulate's (Components/QuantizedDOE.py:47-126) on the slab's share of the height, a step is
+ * ASM_prop.forward over dz (Props/ASM_Prop.py:314-378) with the descriptor's padding and band limit,
+ * unpadded.  With dz = thickness / slices, z_s = s dz, d_s = clamp(h_full - z_s, 0, dz) (d_0 also
+ * carries the base plate), h_full the nearest-upsampled map:
+ *   t_{c,s} = exp(-k_c/2 d_s tand sqrt(eps)) exp(phase_sign i k_c d_s (sqrt(eps) - 1))
+ *   U_{s+1} = ASM_dz(U_s t_s),  s = 0 .. slices-1;  out = U_slices, in the plane `thickness` above the base plate
+ * phase_sign = -1 is DOELayer.modulate's sign (slices = 1 is then thz_asm_forward_modulated over
+ * `thickness`), +1 the sign consistent with the ASM's exp(+i z k_z).  Heights above `thickness` count
+ * as `thickness`, heights below 0 as 0; the map is never read back to the host.
+ *   field / out [B, C, H, W] complex64, height [hs, ws] float32 (all device)
+ * Two kernels per slab (a row pass that inverts, applies the next screen and transforms again in
+ * LDS, and an in-place column pass) on one transfer-function table for every slab; forward only.
+ * No allocation and no synchronisation per call (capturable in a HIP graph once the transform
+ * lengths have been used).  Purely additive: THZ_ABI_VERSION stays 9, a caller detects the entries
+ * by symbol.  Validation, all before any device call: a null pointer, a non-positive size,
+ * thickness or slices, and |phase_sign| != 1 are THZ_E_ARG; padded sides H + 2 pad_h, W + 2 pad_w
+ * other than powers of two from 64 to 8192 (they may differ), slices > 256 and C >
+ * THZ_MAX_WAVELENGTHS are THZ_E_UNSUPPORTED; a short or null workspace THZ_E_WORKSPACE.
+ * Workspace: the row spectra of the H window rows X [BC][H][Pw] and the table [C][Ph][Pw], complex64.
+ */
+typedef struct thz_thick_desc {
+  int B, C, H, W, pad_h, pad_w, bandlimit, hs, ws, slices;
+  float thickness, dx, dy, epsilon, tand, phase_sign;
+  const float* wavelengths; /* host [C] */
+} thz_thick_desc;
+int thz_thick_workspace_size(const thz_thick_desc* d, size_t* bytes);
+int thz_thick_forward(const thz_thick_desc* d, const void* field, const float* height, void* out, void* workspace,
+                      size_t workspace_bytes, thz_stream_t stream);
+
+/*
  * Height-map quantizers of the QAT layers (forward value + custom backward), one fused kernel
  * each way.  weight: [hq, wq] (FP/STE/PSQ/SGV3) or [hq, wq, L] logits (NGS).  height_full:
  * [2hq, 2wq] when mirror (num_unit set, _copy_quad_to_full :28-35) else [hq, wq].

@@ -15,7 +15,7 @@ _ALIASES = ("DataType", "Props", "Components", "LightSource", "utils", "Addons",
 
 _MODULES = ("DataType.ElectricField", "Props.ASM_Prop", "Props.CZT_Prop", "Props.RSC_Prop",
             "Components.QuantizedDOE", "Components.Thin_Lens", "Components.Aperture",
-            "Components.quantization", "Components.discrete_doe",
+            "Components.quantization", "Components.discrete_doe", "Components.ThickDOE",
             "LightSource.Gaussian_beam", "Addons.Field_Resampler", "Addons.Field_Crop", "Addons.Polarization",
             "Addons.Noise", "utils.Noise", "utils.losses", "utils.metrics",
             "utils.units", "utils.Visualization_Helper", "utils.Helper_Functions",

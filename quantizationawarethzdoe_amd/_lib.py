@@ -37,6 +37,7 @@ EXPORTED = [
     "thz_rsc_workspace_size", "thz_rsc_forward",
     "thz_rsc_slice_workspace_size", "thz_rsc_slice_forward",
     "thz_rsc_slice_adjoint_workspace_size", "thz_rsc_slice_adjoint",
+    "thz_thick_workspace_size", "thz_thick_forward",
     "thz_doe_modulate_forward", "thz_doe_modulate_backward", "thz_quant_forward", "thz_quant_backward",
     "thz_doe_quant_backward", "thz_radial_quant_backward",
     "thz_radial_forward", "thz_radial_backward",
@@ -152,6 +153,17 @@ class DoeDesc(ctypes.Structure):
         ("tolerance", ctypes.c_float), ("epsilon", ctypes.c_float), ("tand", ctypes.c_float),
         ("wavelengths", ctypes.POINTER(ctypes.c_float)),
         ("rng", ctypes.c_void_p), ("rng_stream", ctypes.c_uint),
+    ]
+
+
+class ThickDesc(ctypes.Structure):
+    _fields_ = [
+        ("B", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+        ("pad_h", ctypes.c_int), ("pad_w", ctypes.c_int), ("bandlimit", ctypes.c_int),
+        ("hs", ctypes.c_int), ("ws", ctypes.c_int), ("slices", ctypes.c_int),
+        ("thickness", ctypes.c_float), ("dx", ctypes.c_float), ("dy", ctypes.c_float),
+        ("epsilon", ctypes.c_float), ("tand", ctypes.c_float), ("phase_sign", ctypes.c_float),
+        ("wavelengths", ctypes.POINTER(ctypes.c_float)),
     ]
 
 
@@ -328,6 +340,9 @@ def _declare(lib):
     lib.thz_rsc_slice_adjoint_workspace_size.argtypes = [ctypes.POINTER(RscSliceDesc), ctypes.POINTER(c_size_t)]
     lib.thz_rsc_slice_adjoint.argtypes = [ctypes.POINTER(RscSliceDesc), c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p]
+    lib.thz_thick_workspace_size.argtypes = [ctypes.POINTER(ThickDesc), ctypes.POINTER(c_size_t)]
+    lib.thz_thick_forward.argtypes = [ctypes.POINTER(ThickDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]
     lib.thz_doe_modulate_forward.argtypes = [ctypes.POINTER(DoeDesc), c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p]
     lib.thz_doe_modulate_backward.argtypes = [ctypes.POINTER(DoeDesc), c_void_p, c_void_p, c_void_p, c_void_p,

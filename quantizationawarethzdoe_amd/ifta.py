@@ -43,8 +43,13 @@ class IFTAResult:
         self.height, self.idx, self.history = height, idx, history
         self._material, self._device = material, device
 
-    def as_element(self):
-        """The map as a ``FixDOEElement`` with no fabrication tolerance, for the propagators and utils.metrics."""
+    def as_element(self, thick=None):
+        """The map as a ``FixDOEElement`` with no fabrication tolerance, for the propagators and utils.metrics.
+        ``thick=dict(thickness=..., slices=...)`` (and any other ``ThickDOEElement`` keyword): the map as a
+        ``ThickDOEElement`` instead, the split-step model of the relief."""
+        if thick is not None:
+            from .Components.ThickDOE import ThickDOEElement
+            return ThickDOEElement(self.height, material=list(self._material), device=self._device, **thick)
         from .Components.QuantizedDOE import FixDOEElement
         return FixDOEElement(self.height, tolerance=0.0, material=list(self._material), device=self._device)
 

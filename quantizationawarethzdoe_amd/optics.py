@@ -1348,3 +1348,101 @@ def ifta_doe_project(U, doe_shape, wavelength, eps, lut, q=1.0, incident=None):
         _lib.check(_lib.lib().thz_ifta_doe_project(ctypes.byref(d), _p(p), _p(incident), _p(q_dev), _p(h), _p(idx),
                                                    _stream_handle()))
     return h, idx
+
+
+# ---------------------------------------------------------------------------------------------
+# Thick-element DOE: split-step propagation through the relief (thz_thick.hip)
+# ---------------------------------------------------------------------------------------------
+THICK_CONVENTIONS = {"reference": -1.0, "physical": 1.0}
+_THICK_MAX_SLICES = 256
+_THICK_BASE_PLANE = float(np.float32(2e-3))  # DOE_BASE_PLANE (csrc/thz_dev.hpp), BASE_PLANE_THICKNESS of the layers
+
+
+def thick_doe_native(H, W, pad_h, pad_w, slices):
+    """True where thz_thick_forward serves the geometry: padded sides that are powers of two from 64 to
+    8192 (they may differ) and at most 256 slices."""
+    def pow2(n):
+        return 64 <= n <= 8192 and n & (n - 1) == 0
+    return pow2(H + 2 * pad_h) and pow2(W + 2 * pad_w) and slices <= _THICK_MAX_SLICES
+
+
+def _thick_fused(field, height, wavelengths, spacing, eps, tand, thickness, slices, pad_h, pad_w, bl, sign):
+    B, C, H, W = field.shape
+    wl = _lib.float_array(wavelengths)
+    d = _lib.ThickDesc(B=B, C=C, H=H, W=W, pad_h=pad_h, pad_w=pad_w, bandlimit=bl, hs=height.shape[0],
+                       ws=height.shape[1], slices=slices, thickness=thickness, dx=float(spacing[0]),
+                       dy=float(spacing[1]), epsilon=float(eps), tand=float(tand), phase_sign=sign,
+                       wavelengths=_fptr(wl))
+    out = torch.empty_like(field)
+    L = _lib.lib()
+    from .propagation import _launch
+    _launch(L.thz_thick_workspace_size, L.thz_thick_forward, d, field.device, field, height, out)
+    return out
+
+
+def _thick_compose(field, height, wavelengths, spacing, eps, tand, thickness, slices, pad_h, pad_w, bl, sign):
+    from . import doe, propagation
+    dz = float(np.float32(thickness)) / slices  # the library's dz: the fp32 thickness over S, in double
+    u = field
+    for s in range(slices):
+        d = (height - s * dz).clamp(0.0, dz)
+        if s > 0:
+            d = d - _THICK_BASE_PLANE  # the modulate kernel adds the base plate to its argument
+        # sign = +1: U conj(t) = conj(conj(U) t); the kernels read memory, so the conjugates are formed
+        u = doe.modulate(u.conj().resolve_conj() if sign > 0 else u, d, wavelengths, eps, tand)[0]
+        u = propagation.asm_propagate(u.conj().resolve_conj() if sign > 0 else u, wavelengths, spacing, [dz], pad_h,
+                                      pad_w, True, bl)[0]
+    return u
+
+
+def thick_doe(field, height, wavelengths, spacing, eps, tand, thickness, slices, padding_scale=1, bandlimit="exact",
+              convention="reference", method="auto"):
+    """The field behind a DOE of finite thickness: split-step (multi-slice) propagation through the relief.
+
+    ``field`` complex64 [B, C, H, W]; ``height`` float32 [hs, ws], nearest-upsampled to [H, W]; ``thickness`` T
+    > 0 and ``slices`` S >= 1.  With dz = T / S and d_s = clamp(h - s dz, 0, dz) (d_0 also carries the base
+    plate), slab s multiplies by t_s = exp(-k/2 d_s tand sqrt(eps)) exp(sigma i k d_s (sqrt(eps) - 1)) and
+    ASM_prop(z_distance=dz, padding_scale, bandlimit) carries the field to the next slab, cropped every step.
+    The result is the field in the plane T above the base plate; heights above T count as T, below 0 as 0.
+
+    ``convention``: "reference" (sigma = -1, DOELayer.modulate's sign: S = 1 is modulate then ASM over T) or
+    "physical" (sigma = +1, consistent with the ASM's exp(+i z k_z)).  ``bandlimit``: "exact", "approx" or None.
+    ``method``: "fused" -- the thz_thick.hip kernels, two launches per slab, forward only, capturable; padded sides
+    must be powers of two from 64 to 8192 and S <= 256.  "compose" -- the same model as a loop over doe.modulate
+    and the ASM kernels, differentiable in the field and the map.  "auto": fused where it serves the geometry and
+    nothing requires grad, else compose."""
+    who = "thick_doe"
+    _require_device(field, who)
+    if field.dtype != torch.complex64:
+        raise TypeError(f"{who}: the DOE kernels compute in complex64; got {field.dtype}")
+    if field.dim() != 4 or height.dim() != 2:
+        raise ValueError(f"{who}: field [B, C, H, W] and height [hs, ws]; got {tuple(field.shape)}, {tuple(height.shape)}")
+    if convention not in THICK_CONVENTIONS:
+        raise ValueError(f"{who}: convention must be 'reference' or 'physical'; got {convention!r}")
+    if method not in ("auto", "fused", "compose"):
+        raise ValueError(f"{who}: method must be 'auto', 'fused' or 'compose'; got {method!r}")
+    slices = int(slices)
+    thickness = float(np.float32(thickness))
+    if slices < 1 or not thickness > 0.0:
+        raise ValueError(f"{who}: thickness > 0 and slices >= 1; got {thickness}, {slices}")
+    from . import propagation
+    B, C, H, W = field.shape
+    wavelengths = [float(w) for w in wavelengths]
+    if len(wavelengths) != C:
+        raise ValueError(f"{who}: {len(wavelengths)} wavelengths for {C} channels")
+    spacing = (float(spacing[0]), float(spacing[1])) if np.ndim(spacing) else (float(spacing), float(spacing))
+    ps = padding_scale if np.ndim(padding_scale) else (padding_scale, padding_scale)
+    pad_h, pad_w = propagation.asm_padding(H, W, ps)
+    bl = propagation._bandlimit(bandlimit)
+    sign = THICK_CONVENTIONS[convention]
+    diff = torch.is_grad_enabled() and (field.requires_grad or height.requires_grad)
+    native = thick_doe_native(H, W, pad_h, pad_w, slices)
+    if method == "auto":
+        method = "fused" if native and not diff else "compose"
+    height = height.to(device=field.device, dtype=torch.float32)
+    args = (wavelengths, spacing, float(eps), float(tand), thickness, slices, pad_h, pad_w, bl, sign)
+    if method == "compose":
+        return _thick_compose(field, height, *args)
+    if diff:
+        raise RuntimeError(f"{who}: method='fused' is forward only; use method='compose' (or 'auto') for gradients")
+    return _thick_fused(field.detach().contiguous(), height.detach().contiguous(), *args)
