@@ -431,7 +431,8 @@ int thz_asm_forward_modulated(const thz_asm_desc* d, const thz_doe_desc* m, cons
  * as `thickness`, heights below 0 as 0; the map is never read back to the host.
  *   field / out [B, C, H, W] complex64, height [hs, ws] float32 (all device)
  * Two kernels per slab (a row pass that inverts, applies the next screen and transforms again in
- * LDS, and an in-place column pass) on one transfer-function table for every slab; forward only.
+ * LDS, and an in-place column pass) on one transfer-function table for every slab; the backward is
+ * thz_thick_backward, below.
  * No allocation and no synchronisation per call (capturable in a HIP graph once the transform
  * lengths have been used).  Purely additive: THZ_ABI_VERSION stays 9, a caller detects the entries
  * by symbol.  Validation, all before any device call: a null pointer, a non-positive size,
@@ -448,6 +449,49 @@ typedef struct thz_thick_desc {
 int thz_thick_workspace_size(const thz_thick_desc* d, size_t* bytes);
 int thz_thick_forward(const thz_thick_desc* d, const void* field, const float* height, void* out, void* workspace,
                       size_t workspace_bytes, thz_stream_t stream);
+
+/*
+ * Thick-element DOE, native backward (additive: THZ_ABI_VERSION stays 9, detect by symbol).  The
+ * reference has no counterpart; the pieces are DOELayer.modulate's screen and its derivative
+ * (Components/QuantizedDOE.py:47-126, :73-77) and the adjoint of ASM_prop.forward (Props/ASM_Prop.py:314-378).
+ *
+ * One step is A = crop F^-1 diag(H_dz) F pad with the window at the origin of the padded plane, so
+ * A^H = crop F^-1 diag(conj H_dz) F pad: the forward's passes with the table read conjugated.
+ * d_s = clamp(h - z_s, 0, dz) moves with h only in the pixel's ACTIVE SLAB, where t_s' = kappa_c t_s,
+ *   kappa_c = -(k_c/2) tand sqrt(eps) + phase_sign i k_c (sqrt(eps) - 1).
+ * With V_s = U_s t_s and gU_S = grad_out:
+ *   gV_s = A^H gU_{s+1},  gU_s = conj(t_s) gV_s  (s = S-1 .. 0),  grad_field = gU_0
+ *   grad_height[r][c] = sum over b, c and the window pixels p whose nearest source is (r, c) of
+ *                       Re(conj(kappa_c V_{s(p)}(p)) gV_{s(p)}(p)),  s(p) the active slab of p
+ * Active-slab rule, the one definition the saving forward and the backward share: in fp32, with
+ * z_s = (float)(s dz) and dz = (float)(thickness / slices) as the screens use them, slab s is active at a
+ * pixel of height h when 0 < h - z_s < dz and slab s + 1 does not pass the same test (two neighbours can
+ * pass only for h within an ulp of a face; the upper one then counts).  h - z_s is the very value the
+ * screen clamps.  A height exactly on a face, on 0 or on `thickness`, below 0 or above `thickness` has no
+ * active slab and a gradient of exactly 0; torch.clamp's inclusive rule differs on the faces only.
+ *
+ * thz_thick_forward_saved: thz_thick_forward (the same launches, `out` bit-identical) whose first and
+ * middle row passes also store V_s at the pixels whose active slab is s into
+ *   stash [B C][H][W] complex64 (device).  Pixels without an active slab keep what the buffer held: never read.
+ * thz_thick_backward: grad_out [B, C, H, W] complex64, height as in the forward, stash from
+ * thz_thick_forward_saved of the same descriptor, field and map.  grad_field [B, C, H, W] complex64 or NULL
+ * (skipped); grad_height [hs, ws] float32 or NULL (no partials, no reduction; stash may then be NULL).
+ * Launches: one row pass (grad_out rows, zero-padded, FFT), `slices` conjugate column passes, `slices` - 1
+ * middle row passes (IFFT, the height partial where the slab is active, x conj(t_s), FFT), a closing row
+ * pass (s = 0: partial and grad_field) and one reduction whose sums over b, c and the upsample footprint
+ * are fp64 in a fixed order: the result is deterministic, and no atomics are used.
+ * No allocation and no synchronisation per call; capturable on one stream.
+ * Validation as thz_thick_forward, all before any device call: descriptor errors THZ_E_ARG, then
+ * unsupported geometries THZ_E_UNSUPPORTED, then a null data pointer (grad_out, height, both gradients
+ * NULL, grad_height without a stash) THZ_E_ARG, then a short or null workspace THZ_E_WORKSPACE.
+ * Backward workspace: thz_thick_workspace_size + 4 B C H W (the partials, float32) rounded up to 256.
+ */
+int thz_thick_forward_saved(const thz_thick_desc* d, const void* field, const float* height, void* out, void* stash,
+                            void* workspace, size_t workspace_bytes, thz_stream_t stream);
+int thz_thick_backward_workspace_size(const thz_thick_desc* d, size_t* bytes);
+int thz_thick_backward(const thz_thick_desc* d, const void* grad_out, const float* height, const void* stash,
+                       void* grad_field, float* grad_height, void* workspace, size_t workspace_bytes,
+                       thz_stream_t stream);
 
 /*
  * Height-map quantizers of the QAT layers (forward value + custom backward), one fused kernel

@@ -20,16 +20,26 @@ class ThickDOEElement(nn.Module):
     """``ThickDOEElement(height_map, thickness, slices, material, padding_scale=1, convention="reference",
     device=None)``: ``material`` = [epsilon, tan delta]; ``padding_scale`` and the "exact" band limit are
     those of the ASM step between slabs.  ``method`` ("auto", "fused", "compose") may be set on the
-    instance; "auto" runs the fused kernels unless a gradient is asked for."""
+    instance; "auto" runs the fused kernels unless a gradient is asked for.  ``grad="fused"`` (optics.thick_doe)
+    keeps gradients on the fused kernels' native backward; a ``height_map`` handed in as a tensor that requires
+    grad (or an ``nn.Parameter``) is then kept as it is, attached, so the map can be designed on the thick model."""
 
     def __init__(self, height_map, thickness: float, slices: int, material: list = None, padding_scale=1,
-                 convention: str = "reference", device: torch.device = None) -> None:
+                 convention: str = "reference", device: torch.device = None, grad: str = None) -> None:
         super().__init__()
         self.device = device if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
-        h = height_map.detach().clone() if torch.is_tensor(height_map) else torch.tensor(np.asarray(height_map))
-        # a fixed map: no gradient unless the caller asks for one (height_map.requires_grad_(True) sends
-        # "auto" down the differentiable compose path)
-        self.height_map = nn.parameter.Parameter(h.to(device=self.device, dtype=torch.float32), requires_grad=False)
+        if grad not in (None, "fused"):
+            raise ValueError(f"ThickDOEElement: grad must be None or 'fused'; got {grad!r}")
+        self.grad = grad
+        if grad == "fused" and torch.is_tensor(height_map) and height_map.requires_grad:
+            # the map under design: the caller's parameter (registered), or their graph's tensor
+            self.height_map = height_map
+        else:
+            h = height_map.detach().clone() if torch.is_tensor(height_map) else torch.tensor(np.asarray(height_map))
+            # a fixed map: no gradient unless the caller asks for one (height_map.requires_grad_(True) sends
+            # "auto" down the differentiable compose path)
+            self.height_map = nn.parameter.Parameter(h.to(device=self.device, dtype=torch.float32),
+                                                     requires_grad=False)
         if convention not in optics.THICK_CONVENTIONS:
             raise ValueError(f"ThickDOEElement: convention must be 'reference' or 'physical'; got {convention!r}")
         if int(slices) < 1 or not float(thickness) > 0.0:
@@ -52,6 +62,6 @@ class ThickDOEElement(nn.Module):
         out = optics.thick_doe(data, self.height_map, field.wavelengths_host, field.spacing_host,
                                self._eps_tand[0], self._eps_tand[1], self.thickness, self.slices,
                                padding_scale=self.padding_scale, bandlimit=self.bandlimit,
-                               convention=self.convention, method=self.method)
+                               convention=self.convention, method=self.method, grad=self.grad)
         Eout = ElectricField(data=out, wavelengths=field.wavelengths, spacing=field.spacing, device=field.device)
         return Eout._adopt_host(field)

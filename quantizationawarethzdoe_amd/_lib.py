@@ -38,6 +38,7 @@ EXPORTED = [
     "thz_rsc_slice_workspace_size", "thz_rsc_slice_forward",
     "thz_rsc_slice_adjoint_workspace_size", "thz_rsc_slice_adjoint",
     "thz_thick_workspace_size", "thz_thick_forward",
+    "thz_thick_forward_saved", "thz_thick_backward_workspace_size", "thz_thick_backward",
     "thz_doe_modulate_forward", "thz_doe_modulate_backward", "thz_quant_forward", "thz_quant_backward",
     "thz_doe_quant_backward", "thz_radial_quant_backward",
     "thz_radial_forward", "thz_radial_backward",
@@ -343,6 +344,11 @@ def _declare(lib):
     lib.thz_thick_workspace_size.argtypes = [ctypes.POINTER(ThickDesc), ctypes.POINTER(c_size_t)]
     lib.thz_thick_forward.argtypes = [ctypes.POINTER(ThickDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p]
+    lib.thz_thick_forward_saved.argtypes = [ctypes.POINTER(ThickDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_size_t, c_void_p]
+    lib.thz_thick_backward_workspace_size.argtypes = [ctypes.POINTER(ThickDesc), ctypes.POINTER(c_size_t)]
+    lib.thz_thick_backward.argtypes = [ctypes.POINTER(ThickDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]
     lib.thz_doe_modulate_forward.argtypes = [ctypes.POINTER(DoeDesc), c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p]
     lib.thz_doe_modulate_backward.argtypes = [ctypes.POINTER(DoeDesc), c_void_p, c_void_p, c_void_p, c_void_p,
