@@ -1,4 +1,7 @@
-// Device helpers shared by the propagator kernels (ASM, CZT, RSC) and the DOE kernels.
+// Device helpers shared by the propagator kernels (ASM, CZT, RSC) and the DOE kernels: the T / U
+// layouts, sincos and the RS kernel, apertures, the DOE transmission, the counter-based generator
+// (rng_bits, rng_u01, rng_exp1) and the MSE loss sink.  The streaming lane, the fixed-order reduction
+// and the partial sums of the add-on units live in thz_stream.hpp, the noise samplers in thz_noise.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -497,208 +500,5 @@ __device__ __forceinline__ float2 vrs_ez(float2 ex, float2 ey, float x, float y,
   return make_float2((ex.x * x) / r + (ey.x * y) / r, (ex.y * x) / r + (ey.y * y) / r);
 }
 #pragma clang fp contract(on)
-
-// ---------------------------------------------------------------------------------------------
-// The lane of a 16-byte streaming kernel (the polarization kernels of thz_optics.hip, the noise
-// kernels of thz_noise.hip): four elements per lane per round of a grid-stride loop over chunks of
-// POL_CHUNK.  WIDE: four consecutive elements moved as 16-byte accesses (the host picks it only when
-// every pointer is 16-byte aligned; callers that index rows of length m into the arrays also need
-// m % 4 == 0, so that every row starts aligned -- a flat array does not); otherwise element-width
-// accesses, the lane's elements a workgroup apart (coalesced).  A group that crosses n moves element
-// by element under a bound check in either form, which is what serves a flat n with n % 4 != 0.  at(k) is the element index of the lane's k-th value.
-// ---------------------------------------------------------------------------------------------
-constexpr int POL_THREADS = 256;
-constexpr int POL_PX = 4;  // pixels per lane per round
-constexpr int POL_CHUNK = POL_THREADS * POL_PX;
-
-template <bool WIDE>
-struct PolLane {
-  long long p0, n;
-  bool full;  // the four pixels are consecutive, inside n and moved as 16-byte accesses
-  __device__ __forceinline__ PolLane(long long c0, long long n_) : n(n_) {
-    p0 = c0 + (WIDE ? POL_PX * (long long)threadIdx.x : (long long)threadIdx.x);
-    full = WIDE && p0 + (POL_PX - 1) < n;
-  }
-  __device__ __forceinline__ long long at(int k) const { return p0 + (WIDE ? k : k * POL_THREADS); }
-  __device__ __forceinline__ void load(const float2* __restrict__ a, float2 v[POL_PX]) const {
-    if (full) {
-      const float4* q = reinterpret_cast<const float4*>(a + p0);
-      const float4 f0 = q[0], f1 = q[1];
-      v[0] = make_float2(f0.x, f0.y); v[1] = make_float2(f0.z, f0.w);
-      v[2] = make_float2(f1.x, f1.y); v[3] = make_float2(f1.z, f1.w);
-    } else {
-#pragma unroll
-      for (int k = 0; k < POL_PX; ++k) v[k] = at(k) < n ? a[at(k)] : make_float2(0.f, 0.f);
-    }
-  }
-  __device__ __forceinline__ void load(const float* __restrict__ a, float v[POL_PX]) const {
-    if (full) {
-      const float4 f = *reinterpret_cast<const float4*>(a + p0);
-      v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < POL_PX; ++k) v[k] = at(k) < n ? a[at(k)] : 0.f;
-    }
-  }
-  __device__ __forceinline__ void store(float2* __restrict__ a, const float2 v[POL_PX]) const {
-    if (full) {
-      float4* q = reinterpret_cast<float4*>(a + p0);
-      q[0] = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
-      q[1] = make_float4(v[2].x, v[2].y, v[3].x, v[3].y);
-    } else {
-#pragma unroll
-      for (int k = 0; k < POL_PX; ++k)
-        if (at(k) < n) a[at(k)] = v[k];
-    }
-  }
-  __device__ __forceinline__ void store(float* __restrict__ a, const float v[POL_PX]) const {
-    if (full) {
-      *reinterpret_cast<float4*>(a + p0) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < POL_PX; ++k)
-        if (at(k) < n) a[at(k)] = v[k];
-    }
-  }
-  // int32 planes (the level indices of thz_heightmap.hip)
-  __device__ __forceinline__ void load(const int* __restrict__ a, int v[POL_PX]) const {
-    if (full) {
-      const int4 f = *reinterpret_cast<const int4*>(a + p0);
-      v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < POL_PX; ++k) v[k] = at(k) < n ? a[at(k)] : 0;
-    }
-  }
-  __device__ __forceinline__ void store(int* __restrict__ a, const int v[POL_PX]) const {
-    if (full) {
-      *reinterpret_cast<int4*>(a + p0) = make_int4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < POL_PX; ++k)
-        if (at(k) < n) a[at(k)] = v[k];
-    }
-  }
-};
-
-// ---------------------------------------------------------------------------------------------
-// Detector-noise samplers (Addons/Noise.py:27,58,87-89, utils/Noise.py:32) on the counter-based
-// generator above: pure functions of (rng state, stream, element index, parameters), so a forward
-// and its backward regenerate the same draw and a result never depends on the launch geometry or
-// on what a neighbouring lane does.  fp32, contraction off.
-// ---------------------------------------------------------------------------------------------
-#pragma clang fp contract(off)
-// Two independent standard normals from one rng_bits word (torch.randn): Box-Muller on two 24-bit
-// uniforms, r = sqrt(-2 log u1) with u1 = (b1 + 1) / 2^24 in (0, 1] as in rng_exp1 (log(0) cannot
-// occur), angle u2 = b2 / 2^24 in [0, 1) revolutions -- the unit of v_sin_f32 / v_cos_f32 -- giving
-// (r cos, r sin).  The smallest u1 bounds |n| by sqrt(2 * 24 * ln 2) = 5.768 (the normal mass beyond
-// it is 8e-9).  A real draw takes .x; a complex draw takes both.
-__device__ __forceinline__ float2 rng_normal2(const unsigned* rng, unsigned stream, unsigned idx) {
-  const unsigned long long w = rng_bits(rng, stream, idx);
-  const float u1 = (float)((unsigned)(w >> 40) + 1u) * (1.0f / 16777216.0f);
-  const float u2 = (float)((unsigned)(w >> 16) & 0xFFFFFFu) * (1.0f / 16777216.0f);
-  const float r = sqrtf(-2.0f * logf(u1));
-  return make_float2(r * __builtin_amdgcn_cosf(u2), r * __builtin_amdgcn_sinf(u2));
-}
-__device__ __forceinline__ float rng_normal(const unsigned* rng, unsigned stream, unsigned idx) {
-  return rng_normal2(rng, stream, idx).x;
-}
-// complex standard normal, variance 1 in total (torch.randn of a complex dtype: 1/2 per component)
-__device__ __forceinline__ float2 rng_cnormal(const unsigned* rng, unsigned stream, unsigned idx) {
-  const float2 z = rng_normal2(rng, stream, idx);
-  return make_float2(z.x * 0.70710678118654752f, z.y * 0.70710678118654752f);
-}
-
-// Poisson(lam) (torch.poisson), returned as a float.  lam = 0 gives 0; lam < 0 or NaN gives NaN (no
-// host check: that would be a sync).  Rates up to 2^24 are supported (beyond it fp32 no longer holds
-// every count); the tests cover 0.05 to 1e5.
-//
-// Attempt j of element idx draws word j of a splitmix64 sequence of its own, seeded with the
-// element's base word rng_bits(state, stream ^ "POIS", idx): w_j = mix(base + (j + 1) gamma).  The
-// attempt number enters the 64-bit counter in a hash round of its own and never the 32-bit stream,
-// so (stream, j) pairs cannot alias: two streams' attempt sequences start from two hashed 64-bit
-// words and meet only if those differ by a small multiple of gamma (probability ~2^-60 per pair).
-// No w_j is the base word itself, so the Poisson draws of a stream are also apart from its normal /
-// uniform draws, and a lane's sample does not depend on how long its neighbours loop.
-//
-// lam < 10: inversion by sequential search in fp64 on a 53-bit uniform (a 24-bit uniform could not
-// reach the tail mass below 2^-24).  P(X >= 64 | lam < 10) < 4e-30, far below the uniform's 2^-53
-// resolution, so the search bound of 64 only stops a cumulative sum that rounding left below u.
-//
-// lam >= 10: Hoermann's transformed rejection with squeeze (PTRS, Insurance: Mathematics and
-// Economics 12 (1993) 39-45; the algorithm of numpy and of torch's CPU poisson), fp32.  U has 23
-// bits and is centred ((b + 1/2) / 2^23 - 1/2, never 0 or +-1/2), V = (b + 1) / 2^24 in (0, 1].  An
-// attempt accepts with probability 1 / invalpha: 0.75 at lam = 10, above 0.85 from lam = 90, 0.89
-// in the limit; the squeeze alone (no log, no lgamma) accepts 0.35 - 0.80.  The loop runs until the
-// lane accepts: there is no attempt cap, since returning early would bias the sample.
-//
-// The acceptance test compares with log pmf(k) = -lam + k log lam - lgamma(k + 1)
-// (rng_poisson_logpmf).  Evaluated as written, with lgammaf, its terms are ~lam log lam and cancel
-// to a few units: the result would carry 1e-3 absolute at lam = 1000 and 0.1 at 1e5.  So that form
-// serves k < 16 only (small terms, or a candidate so far below lam that it is rejected whatever the
-// rounding); from k = 16 Stirling's series for lgamma is folded in analytically, with d = k - lam
-// and t = d / lam,
-//   log pmf = -d t + k (t - log1p(t)) - log(2 pi k) / 2 - 1 / (12 k) + 1 / (360 k^3)   (+ < 1e-9),
-// whose terms are of the size of d: ~1e-5 absolute at lam = 1000, ~1e-4 at 1e5.
-constexpr unsigned RNG_POISSON_STREAM = 0x504F4953u;  // "POIS"
-__device__ __forceinline__ unsigned long long rng_poisson_word(unsigned long long base, unsigned attempt) {
-  unsigned long long x = base + ((unsigned long long)attempt + 1ull) * 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-__device__ __forceinline__ float rng_poisson_logpmf(float k, float lam, float loglam) {
-  if (k < 16.0f) return -lam + k * loglam - lgammaf(k + 1.0f);
-  const float d = k - lam, t = d / lam, ik = 1.0f / k;
-  return (-d * t + k * (t - log1pf(t))) - 0.5f * logf(6.2831853071795865f * k) -
-         ik * (0.083333333333333333f - 0.0027777777777777778f * ik * ik);
-}
-__device__ inline float rng_poisson(const unsigned* rng, unsigned stream, unsigned idx, float lam) {
-  if (!(lam >= 0.0f)) return __builtin_nanf("");
-  if (lam == 0.0f) return 0.0f;
-  const unsigned long long base = rng_bits(rng, stream ^ RNG_POISSON_STREAM, idx);
-  if (lam < 10.0f) {
-    const double u = (double)(rng_poisson_word(base, 0u) >> 11) * 0x1p-53;
-    const double l = (double)lam;
-    double p = exp(-l), s = p;
-    int k = 0;
-    while (u >= s && k < 64) {
-      ++k;
-      p *= l / (double)k;
-      s += p;
-    }
-    return (float)k;
-  }
-  const float slam = sqrtf(lam), loglam = logf(lam);
-  const float b = 0.931f + 2.53f * slam;
-  const float a = -0.059f + 0.02483f * b;
-  const float invalpha = 1.1239f + 1.1328f / (b - 3.4f);
-  const float vr = 0.9277f - 3.6224f / (b - 2.0f);
-  for (unsigned j = 0u;; ++j) {
-    const unsigned long long w = rng_poisson_word(base, j);
-    const float U = ((float)(unsigned)(w >> 41) + 0.5f) * (1.0f / 8388608.0f) - 0.5f;
-    const float V = (float)(((unsigned)(w >> 16) & 0xFFFFFFu) + 1u) * (1.0f / 16777216.0f);
-    const float us = 0.5f - fabsf(U);
-    const float k = floorf((2.0f * a / us + b) * U + lam + 0.43f);
-    if (us >= 0.07f && V <= vr) return k;
-    if (k < 0.0f || (us < 0.013f && V > us)) continue;
-    if (logf(V) + logf(invalpha) - logf(a / (us * us) + b) <= rng_poisson_logpmf(k, lam, loglam)) return k;
-  }
-}
-#pragma clang fp contract(on)
-
-// Sum of one double per thread over the workgroup in a fixed order (xor butterfly inside a wave,
-// then the waves in index order); the result is valid in thread 0.  Every thread must call it.
-__device__ __forceinline__ double block_sum_fixed(double v) {
-  __shared__ double s_w[16];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if (lane == 0) s_w[wid] = v;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < nw; ++w) v += s_w[w];
-  return v;
-}
 
 }  // namespace thz

@@ -25,6 +25,7 @@
 
 #include "thz_common.hpp"
 #include "thz_dev.hpp"
+#include "thz_stream.hpp"
 #include "thz_launch.hpp"
 
 namespace thz {
@@ -47,33 +48,33 @@ __device__ __forceinline__ void lut_to_lds(const LutArgs& a, float* s_lut) {
 }
 
 template <int MODE, bool WIDE>
-__global__ void __launch_bounds__(POL_THREADS) lut_quantize_fwd_kernel(LutArgs a, const float* __restrict__ x,
+__global__ void __launch_bounds__(LANE_THREADS) lut_quantize_fwd_kernel(LutArgs a, const float* __restrict__ x,
                                                                        long long n, float* __restrict__ q,
                                                                        int* __restrict__ idx) {
   __shared__ float s_lut[THZ_MAX_LUT];
   lut_to_lds(a, s_lut);
-  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < n; c0 += (long long)gridDim.x * POL_CHUNK) {
-    const PolLane<WIDE> lane(c0, n);
-    float v[POL_PX], qo[POL_PX];
-    int io[POL_PX];
+  for (long long c0 = (long long)blockIdx.x * LANE_CHUNK; c0 < n; c0 += (long long)gridDim.x * LANE_CHUNK) {
+    const Lane4<WIDE> lane(c0, n);
+    float v[LANE_PX], qo[LANE_PX];
+    int io[LANE_PX];
     lane.load(x, v);
     if (MODE == THZ_LUTQ_BUCKETIZE) {
 #pragma unroll
-      for (int k = 0; k < POL_PX; ++k) io[k] = 0;
+      for (int k = 0; k < LANE_PX; ++k) io[k] = 0;
       for (int j = 0; j < a.T; ++j) {  // wave-uniform j: the threshold is a scalar operand
         const float t = a.thr[j];
 #pragma unroll
-        for (int k = 0; k < POL_PX; ++k) io[k] += !(t > v[k]);  // upper bound; NaN counts every threshold
+        for (int k = 0; k < LANE_PX; ++k) io[k] += !(t > v[k]);  // upper bound; NaN counts every threshold
       }
 #pragma unroll
-      for (int k = 0; k < POL_PX; ++k) {
+      for (int k = 0; k < LANE_PX; ++k) {
         if (a.wrap && io[k] == a.T) io[k] = 0;  // io <= T, so this is io mod T
         qo[k] = s_lut[io[k]];  // io < L by the host's check of T
       }
     } else {
-      float best[POL_PX];
+      float best[LANE_PX];
 #pragma unroll
-      for (int k = 0; k < POL_PX; ++k) {
+      for (int k = 0; k < LANE_PX; ++k) {
         io[k] = 0;
         qo[k] = a.lut[0];
         best[k] = fabsf(v[k] - qo[k]);
@@ -81,7 +82,7 @@ __global__ void __launch_bounds__(POL_THREADS) lut_quantize_fwd_kernel(LutArgs a
       for (int j = 1; j < a.L; ++j) {
         const float l = a.lut[j];
 #pragma unroll
-        for (int k = 0; k < POL_PX; ++k) {
+        for (int k = 0; k < LANE_PX; ++k) {
           const float dj = fabsf(v[k] - l);
           if (dj < best[k]) {  // strict: ties keep the lower index; NaN never wins
             best[k] = dj;
@@ -123,7 +124,7 @@ __device__ __forceinline__ float lut_slope(float x, int i, float s, int L, const
 }
 
 template <int KIND, bool WIDE>
-__global__ void __launch_bounds__(POL_THREADS) lut_quantize_bwd_kernel(LutArgs a, const float* __restrict__ x,
+__global__ void __launch_bounds__(LANE_THREADS) lut_quantize_bwd_kernel(LutArgs a, const float* __restrict__ x,
                                                                        const int* __restrict__ idx,
                                                                        const float* __restrict__ g,
                                                                        const float* __restrict__ s_dev, long long n,
@@ -131,25 +132,25 @@ __global__ void __launch_bounds__(POL_THREADS) lut_quantize_bwd_kernel(LutArgs a
   __shared__ float s_lut[THZ_MAX_LUT];
   lut_to_lds(a, s_lut);
   const float s = KIND == THZ_LUTQ_GRAD_IDENTITY ? 1.0f : *s_dev;
-  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < n; c0 += (long long)gridDim.x * POL_CHUNK) {
-    const PolLane<WIDE> lane(c0, n);
-    float v[POL_PX], gv[POL_PX], o[POL_PX];
-    int iv[POL_PX];
+  for (long long c0 = (long long)blockIdx.x * LANE_CHUNK; c0 < n; c0 += (long long)gridDim.x * LANE_CHUNK) {
+    const Lane4<WIDE> lane(c0, n);
+    float v[LANE_PX], gv[LANE_PX], o[LANE_PX];
+    int iv[LANE_PX];
     lane.load(g, gv);
     if (KIND != THZ_LUTQ_GRAD_IDENTITY) {
       lane.load(x, v);
       lane.load(idx, iv);
     }
 #pragma unroll
-    for (int k = 0; k < POL_PX; ++k) o[k] = gv[k] * lut_slope<KIND>(v[k], iv[k], s, a.L, s_lut);
+    for (int k = 0; k < LANE_PX; ++k) o[k] = gv[k] * lut_slope<KIND>(v[k], iv[k], s, a.L, s_lut);
     lane.store(out, o);
   }
 }
 
 // ---- total variation -------------------------------------------------------------------------
-constexpr int TV_COLS = 64 * POL_PX;  // a wave's tile: 256 columns (four per lane) ...
+constexpr int TV_COLS = 64 * LANE_PX;  // a wave's tile: 256 columns (four per lane) ...
 constexpr int TV_ROWS = 32;           // ... by 32 rows
-constexpr int TV_WAVES = POL_THREADS / 64;
+constexpr int TV_WAVES = LANE_THREADS / 64;
 constexpr int TV_MAX_EDGE = 1 << 30;  // rows / columns: a tile's end (edge + tile size) stays an int
 
 struct TvShape {
@@ -173,33 +174,19 @@ struct TvTile {
     plane = n * s.H * s.W;
     r0 = (int)(rem / s.tx) * TV_ROWS;  // < H + TV_ROWS and c0 < W + TV_COLS: ints by tv_shape's bound on H, W
     r1 = r0 + TV_ROWS < s.H ? r0 + TV_ROWS : s.H;
-    c0 = (int)(rem % s.tx) * TV_COLS + (threadIdx.x & 63) * POL_PX;
+    c0 = (int)(rem % s.tx) * TV_COLS + (threadIdx.x & 63) * LANE_PX;
   }
 };
 
-// the lane's four values of row i, zero outside the plane
+// the lane's four values of row i, zero outside the plane (a row outside it has no columns)
 __device__ __forceinline__ void tv_row(const float* __restrict__ p, const TvShape& s, const TvTile& t, int i,
-                                       float v[POL_PX]) {
+                                       float v[LANE_PX]) {
   const bool in = i >= 0 && i < s.H;
-  const float* row = p + t.plane + (long long)(in ? i : 0) * s.W;
-  if (in && s.wide && t.c0 < s.W) {  // W % 4 == 0: c0 < W means c0 + 3 < W
-    const float4 f = *reinterpret_cast<const float4*>(row + t.c0);
-    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < POL_PX; ++k) v[k] = in && t.c0 + k < s.W ? row[t.c0 + k] : 0.0f;
-  }
+  ld4(p + t.plane + (long long)(in ? i : 0) * s.W, t.c0, in ? s.W : 0, s.wide, v);
 }
 __device__ __forceinline__ void tv_store(float* __restrict__ p, const TvShape& s, const TvTile& t, int i,
-                                         const float v[POL_PX]) {
-  float* row = p + t.plane + (long long)i * s.W;
-  if (s.wide && t.c0 < s.W) {
-    *reinterpret_cast<float4*>(row + t.c0) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < POL_PX; ++k)
-      if (t.c0 + k < s.W) row[t.c0 + k] = v[k];
-  }
+                                         const float v[LANE_PX]) {
+  st4(p + t.plane + (long long)i * s.W, t.c0, s.W, s.wide, v);
 }
 
 // xx[0 .. 2 D + 3] = row i at columns c0 - D .. c0 + 3 + D: the lane's own four (v), the D beside them from
@@ -207,20 +194,20 @@ __device__ __forceinline__ void tv_store(float* __restrict__ p, const TvShape& s
 // Every lane of the wave calls it.
 template <int D>
 __device__ __forceinline__ void tv_span(const float* __restrict__ p, const TvShape& s, const TvTile& t, int i,
-                                        const float v[POL_PX], float xx[POL_PX + 2 * D]) {
+                                        const float v[LANE_PX], float xx[LANE_PX + 2 * D]) {
   const int lane = threadIdx.x & 63;
   const bool in = i >= 0 && i < s.H;
   const float* row = p + t.plane + (long long)(in ? i : 0) * s.W;
 #pragma unroll
-  for (int k = 0; k < POL_PX; ++k) xx[D + k] = v[k];
+  for (int k = 0; k < LANE_PX; ++k) xx[D + k] = v[k];
 #pragma unroll
   for (int e = 1; e <= D; ++e) {
-    float l = __shfl_up(v[POL_PX - e], 1), r = __shfl_down(v[e - 1], 1);
-    const int cl = t.c0 - e, cr = t.c0 + POL_PX - 1 + e;
+    float l = __shfl_up(v[LANE_PX - e], 1), r = __shfl_down(v[e - 1], 1);
+    const int cl = t.c0 - e, cr = t.c0 + LANE_PX - 1 + e;
     if (lane == 0) l = in && cl >= 0 && cl < s.W ? row[cl] : 0.0f;
     if (lane == 63) r = in && cr < s.W ? row[cr] : 0.0f;
     xx[D - e] = l;
-    xx[D + POL_PX - 1 + e] = r;
+    xx[D + LANE_PX - 1 + e] = r;
   }
 }
 
@@ -230,23 +217,23 @@ __device__ __forceinline__ float tv_sign(float v) { return (float)((v > 0.0f) - 
 
 // SUMS: partial[2 block + {0, 1}] = the workgroup's sum |dx|, sum |dy|; else dx, dy are written
 template <bool SUMS>
-__global__ void __launch_bounds__(POL_THREADS) tv_fwd_kernel(TvShape s, const float* __restrict__ x,
+__global__ void __launch_bounds__(LANE_THREADS) tv_fwd_kernel(TvShape s, const float* __restrict__ x,
                                                              float* __restrict__ dx, float* __restrict__ dy,
                                                              double* __restrict__ partial) {
   const TvTile t(s);
   const float cw = (float)((double)s.W / 4.0), ch = (float)((double)s.H / 4.0);
   double sx = 0.0, sy = 0.0;
   if (t.valid) {  // wave-uniform
-    float up[POL_PX], cur[POL_PX], dn[POL_PX];
+    float up[LANE_PX], cur[LANE_PX], dn[LANE_PX];
     tv_row(x, s, t, t.r0 - 1, up);
     tv_row(x, s, t, t.r0, cur);
     for (int i = t.r0; i < t.r1; ++i) {
       tv_row(x, s, t, i + 1, dn);
-      float xx[POL_PX + 2], ox[POL_PX], oy[POL_PX];
+      float xx[LANE_PX + 2], ox[LANE_PX], oy[LANE_PX];
       tv_span<1>(x, s, t, i, cur, xx);
       const bool row_in = i >= 1 && i <= s.H - 2;
 #pragma unroll
-      for (int k = 0; k < POL_PX; ++k) {
+      for (int k = 0; k < LANE_PX; ++k) {
         const int c = t.c0 + k;
         ox[k] = c >= 1 && c <= s.W - 2 ? cw * tv_stencil(xx[k], xx[k + 1], xx[k + 2]) : 0.0f;
         oy[k] = row_in && c < s.W ? ch * tv_stencil(up[k], cur[k], dn[k]) : 0.0f;
@@ -263,32 +250,20 @@ __global__ void __launch_bounds__(POL_THREADS) tv_fwd_kernel(TvShape s, const fl
       }
     }
   }
-  if (SUMS) {
-    sx = block_sum_fixed(sx);
-    sy = block_sum_fixed(sy);
-    if (threadIdx.x == 0) {
-      partial[(size_t)blockIdx.x * 2] = sx;
-      partial[(size_t)blockIdx.x * 2 + 1] = sy;
-    }
-  }
+  if (SUMS) store_partials(Sums<2>{{sx, sy}}, partial, blockIdx.x);
 }
 
 // tv = sum |dx| / count + sum |dy| / count, the partials added in index order
-__global__ void __launch_bounds__(POL_THREADS) tv_finish_kernel(const double* __restrict__ partial, long long blocks,
+__global__ void __launch_bounds__(LANE_THREADS) tv_finish_kernel(const double* __restrict__ partial, long long blocks,
                                                                 double count, float* __restrict__ tv) {
-  double m[2];
-  for (int k = 0; k < 2; ++k) {
-    double acc = 0.0;
-    for (long long i = threadIdx.x; i < blocks; i += POL_THREADS) acc += partial[(size_t)i * 2 + k];
-    m[k] = block_sum_fixed(acc) / count;
-  }
-  if (threadIdx.x == 0) *tv = (float)(m[0] + m[1]);
+  const Sums<2> a = gather_partials<2>(partial, blocks);
+  if (threadIdx.x == 0) *tv = (float)(a.v[0] / count + a.v[1] / count);
 }
 
 // FROM_X: u, v = sign(dx), sign(dy) recomputed from x (a), scaled by *grad_loss / (N H W);
 // else u = a (the cotangent of dx), v = b (the cotangent of dy)
 template <bool FROM_X>
-__global__ void __launch_bounds__(POL_THREADS) tv_bwd_kernel(TvShape s, const float* __restrict__ a,
+__global__ void __launch_bounds__(LANE_THREADS) tv_bwd_kernel(TvShape s, const float* __restrict__ a,
                                                              const float* __restrict__ b,
                                                              const float* __restrict__ grad_loss,
                                                              float* __restrict__ grad) {
@@ -299,26 +274,26 @@ __global__ void __launch_bounds__(POL_THREADS) tv_bwd_kernel(TvShape s, const fl
   const double cnt = FROM_X ? (double)s.N * (double)s.H * (double)s.W : 1.0;
   const float cw = (float)((double)s.W / (4.0 * cnt)), ch = (float)((double)s.H / (4.0 * cnt));
   const float gl = FROM_X ? *grad_loss : 1.0f;
-  float win[2 * D + 1][POL_PX];  // rows i - D .. i + D of vsrc
+  float win[2 * D + 1][LANE_PX];  // rows i - D .. i + D of vsrc
 #pragma unroll
   for (int r = 1; r <= 2 * D; ++r) tv_row(vsrc, s, t, t.r0 - D + r - 1, win[r]);
   for (int i = t.r0; i < t.r1; ++i) {
 #pragma unroll
     for (int r = 0; r < 2 * D; ++r)
 #pragma unroll
-      for (int k = 0; k < POL_PX; ++k) win[r][k] = win[r + 1][k];
+      for (int k = 0; k < LANE_PX; ++k) win[r][k] = win[r + 1][k];
     tv_row(vsrc, s, t, i + D, win[2 * D]);
-    float hrow[POL_PX], xx[POL_PX + 2 * D], u[POL_PX + 2], o[POL_PX];
+    float hrow[LANE_PX], xx[LANE_PX + 2 * D], u[LANE_PX + 2], o[LANE_PX];
     if constexpr (FROM_X) {
 #pragma unroll
-      for (int k = 0; k < POL_PX; ++k) hrow[k] = win[D][k];
+      for (int k = 0; k < LANE_PX; ++k) hrow[k] = win[D][k];
     } else {
       tv_row(a, s, t, i, hrow);
     }
     tv_span<D>(a, s, t, i, hrow, xx);
     // u at columns c0 - 1 .. c0 + 4, zero outside the interior columns
 #pragma unroll
-    for (int k = 0; k < POL_PX + 2; ++k) {
+    for (int k = 0; k < LANE_PX + 2; ++k) {
       const int c = t.c0 - 1 + k;
       float val;
       if constexpr (FROM_X) val = tv_sign(tv_stencil(xx[k], xx[k + 1], xx[k + 2]));
@@ -326,7 +301,7 @@ __global__ void __launch_bounds__(POL_THREADS) tv_bwd_kernel(TvShape s, const fl
       u[k] = c >= 1 && c <= s.W - 2 ? val : 0.0f;
     }
 #pragma unroll
-    for (int k = 0; k < POL_PX; ++k) {
+    for (int k = 0; k < LANE_PX; ++k) {
       float v[3];  // rows i - 1, i, i + 1, zero outside the interior rows
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
@@ -346,21 +321,8 @@ __global__ void __launch_bounds__(POL_THREADS) tv_bwd_kernel(TvShape s, const fl
 #pragma clang fp contract(on)
 
 // ---- host side -------------------------------------------------------------------------------
-static bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-static int check_ptrs(const char* who, std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs) {
-    if (!p) return fail(THZ_E_ARG, "%s: null pointer", who);
-    if (misaligned(p, 4)) return fail(THZ_E_ARG, "%s: array not 4-byte aligned", who);
-  }
-  return THZ_OK;
-}
-
-static bool all_aligned16(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if (misaligned(p, 16)) return false;  // a null pointer is aligned
-  return true;
-}
+// every array of this unit is float32 or int32
+static int check_ptrs(const char* who, std::initializer_list<const void*> ptrs) { return check_arrays(who, ptrs, 4); }
 
 static int lut_check(const char* who, const thz_lut_quantize_desc* d, bool forward) {
   if (!d) return fail(THZ_E_ARG, "%s: null descriptor", who);
@@ -423,10 +385,10 @@ extern "C" int thz_lut_quantize_forward(const thz_lut_quantize_desc* d, const fl
   if (d->n == 0) return THZ_OK;
   hipStream_t s = (hipStream_t)stream;
   int blocks = 0;
-  if (int e = stream_grid((d->n + POL_CHUNK - 1) / POL_CHUNK, &blocks)) return e;
+  if (int e = stream_grid((d->n + LANE_CHUNK - 1) / LANE_CHUNK, &blocks)) return e;
   const LutArgs a = lut_args(d);
   const bool wide = all_aligned16({x, q, idx});
-  const dim3 g((unsigned)blocks), b(POL_THREADS);
+  const dim3 g((unsigned)blocks), b(LANE_THREADS);
   KernelTimer kt("lut_quantize_fwd", s);
   auto launch = [&](auto MODE) {
     if (wide) hipLaunchKernelGGL((lut_quantize_fwd_kernel<MODE(), true>), g, b, 0, s, a, x, d->n, q, idx);
@@ -451,10 +413,10 @@ extern "C" int thz_lut_quantize_backward(const thz_lut_quantize_desc* d, const f
   if (d->n == 0) return THZ_OK;
   hipStream_t s = (hipStream_t)stream;
   int blocks = 0;
-  if (int e = stream_grid((d->n + POL_CHUNK - 1) / POL_CHUNK, &blocks)) return e;
+  if (int e = stream_grid((d->n + LANE_CHUNK - 1) / LANE_CHUNK, &blocks)) return e;
   const LutArgs a = lut_args(d);
   const bool wide = identity ? all_aligned16({grad_out, grad_in}) : all_aligned16({x, idx, grad_out, grad_in});
-  const dim3 g((unsigned)blocks), b(POL_THREADS);
+  const dim3 g((unsigned)blocks), b(LANE_THREADS);
   KernelTimer kt("lut_quantize_bwd", s);
   auto launch = [&](auto KIND) {
     if (wide)
@@ -487,7 +449,7 @@ extern "C" int thz_tv_forward(const float* x, long long N, int H, int W, float* 
   if (int e = check_ptrs(who, {x})) return e;
   if ((dx == nullptr) != (dy == nullptr)) return fail(THZ_E_ARG, "%s: dx and dy go together", who);
   hipStream_t s = (hipStream_t)stream;
-  const dim3 g((unsigned)tv_blocks(sh)), b(POL_THREADS);
+  const dim3 g((unsigned)tv_blocks(sh)), b(LANE_THREADS);
   if (dx) {
     if (int e = check_ptrs(who, {dx, dy})) return e;
     sh.wide = W % 4 == 0 && all_aligned16({x, dx, dy});
@@ -521,7 +483,7 @@ extern "C" int thz_tv_backward(const float* x, const float* gdx, const float* gd
   if (int e = tv_shape(who, N, H, W, &sh)) return e;
   if (int e = check_ptrs(who, {grad})) return e;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 g((unsigned)tv_blocks(sh)), b(POL_THREADS);
+  const dim3 g((unsigned)tv_blocks(sh)), b(LANE_THREADS);
   if (x) {
     if (gdx || gdy) return fail(THZ_E_ARG, "%s: x (total_variation) or gdx, gdy (center_difference), not both", who);
     if (int e = check_ptrs(who, {x, grad_loss})) return e;

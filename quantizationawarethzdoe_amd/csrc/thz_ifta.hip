@@ -7,7 +7,7 @@
 //                            S_TU = sum_M T |U|, S_TT = sum_M T^2 in fp64, then s = S_TU / S_TT and
 //                            eff = S_in / S_all.  A workgroup owns IF_CHUNK consecutive pixels of a plane (a
 //                            lane four consecutive pixels per step) and writes its four sums to the
-//                            workspace (block_sum_fixed); ifta_stats_finish_kernel adds a plane's chunks
+//                            workspace (store_partials); ifta_stats_finish_kernel adds a plane's chunks
 //                            in index order.  No atomics: the same input gives the same bits.
 //   thz_ifta_target_project  inside M: a' = max(0, alpha s T + (1 - alpha) |U|), out = a' U / |U| (a' where
 //                            |U| = 0); outside: out = beta U.  s is read from device memory.  Each pixel
@@ -28,6 +28,7 @@
 
 #include "thz_common.hpp"
 #include "thz_dev.hpp"
+#include "thz_stream.hpp"
 #include "thz_launch.hpp"
 
 namespace thz {
@@ -54,30 +55,15 @@ struct IfShape {
 template <bool MASK>
 __device__ __forceinline__ void if_load(const IfShape& s, const float2* u, const float* t, const unsigned char* m,
                                         long long i, float2 v[IF_PX], float tv[IF_PX], bool in[IF_PX]) {
-  if (s.wide && i + (IF_PX - 1) < s.HW) {
-    uint4 raw[2];
-    const uint4* q = reinterpret_cast<const uint4*>(u + i);
-    raw[0] = q[0];
-    raw[1] = q[1];
-    __builtin_memcpy(v, raw, sizeof(raw));
-    const uint4 rt = *reinterpret_cast<const uint4*>(t + i);
-    __builtin_memcpy(tv, &rt, sizeof(rt));
-    if (MASK) {
-      const unsigned rm = *reinterpret_cast<const unsigned*>(m + i);
+  ld4(u, i, s.HW, s.wide, v);
+  ld4(t, i, s.HW, s.wide, tv);
+  if (MASK && s.wide && i + (IF_PX - 1) < s.HW) {  // the mask's four bytes as one access
+    const unsigned rm = *reinterpret_cast<const unsigned*>(m + i);
 #pragma unroll
-      for (int k = 0; k < IF_PX; ++k) in[k] = ((rm >> (8 * k)) & 0xffu) != 0u;
-    } else {
-#pragma unroll
-      for (int k = 0; k < IF_PX; ++k) in[k] = true;
-    }
+    for (int k = 0; k < IF_PX; ++k) in[k] = ((rm >> (8 * k)) & 0xffu) != 0u;
   } else {
 #pragma unroll
-    for (int k = 0; k < IF_PX; ++k) {
-      const bool ok = i + k < s.HW;
-      v[k] = ok ? u[i + k] : make_float2(0.0f, 0.0f);
-      tv[k] = ok ? t[i + k] : 0.0f;
-      in[k] = ok && (MASK ? m[i + k] != 0 : true);
-    }
+    for (int k = 0; k < IF_PX; ++k) in[k] = i + k < s.HW && (MASK ? m[i + k] != 0 : true);
   }
 }
 
@@ -112,29 +98,15 @@ __global__ void __launch_bounds__(IF_THREADS) ifta_stats_kernel(IfShape s, const
       }
     }
   }
-  s_all = block_sum_fixed(s_all);
-  s_in = block_sum_fixed(s_in);
-  s_tu = block_sum_fixed(s_tu);
-  s_tt = block_sum_fixed(s_tt);
-  if (threadIdx.x == 0) {
-    double* o = partial + (size_t)blockIdx.x * IF_SUMS;
-    o[0] = s_all; o[1] = s_in; o[2] = s_tu; o[3] = s_tt;
-  }
+  store_partials(Sums<IF_SUMS>{{s_all, s_in, s_tu, s_tt}}, partial, blockIdx.x);
 }
 
-// out[n 6 ..]: one workgroup per plane adds the plane's chunks, each thread its chunks in ascending
-// order, then block_sum_fixed
+// out[n 6 ..]: one workgroup per plane adds the plane's chunks (gather_partials)
 __global__ void __launch_bounds__(IF_THREADS) ifta_stats_finish_kernel(IfShape s, const double* __restrict__ partial,
                                                                        double* __restrict__ out) {
   const long long n = blockIdx.x;
-  double a[IF_SUMS] = {0.0, 0.0, 0.0, 0.0};
-  for (long long c = threadIdx.x; c < s.chunks; c += IF_THREADS) {
-    const double* p = partial + (size_t)(n * s.chunks + c) * IF_SUMS;
-#pragma unroll
-    for (int k = 0; k < IF_SUMS; ++k) a[k] += p[k];
-  }
-#pragma unroll
-  for (int k = 0; k < IF_SUMS; ++k) a[k] = block_sum_fixed(a[k]);
+  const Sums<IF_SUMS> sums = gather_partials<IF_SUMS>(partial, s.chunks, n * s.chunks);
+  const double* a = sums.v;
   if (threadIdx.x == 0) {
     double* o = out + (size_t)n * IF_STATS;
     o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3];
@@ -178,17 +150,7 @@ __global__ void __launch_bounds__(IF_THREADS) ifta_project_kernel(IfShape s, con
         r[k] = make_float2((float)(s.beta * x), (float)(s.beta * y));
       }
     }
-    if (s.wide && i + (IF_PX - 1) < s.HW) {
-      uint4 raw[2];
-      __builtin_memcpy(raw, r, sizeof(raw));
-      uint4* q = reinterpret_cast<uint4*>(o + i);
-      q[0] = raw[0];
-      q[1] = raw[1];
-    } else {
-#pragma unroll
-      for (int k = 0; k < IF_PX; ++k)
-        if (i + k < s.HW) o[i + k] = r[k];
-    }
+    st4(o, i, s.HW, s.wide, r);
   }
 }
 
@@ -310,8 +272,6 @@ __global__ void __launch_bounds__(DP_THREADS) ifta_doe_kernel(DpArgs a, const fl
 #pragma clang fp contract(on)
 
 // ---- host side -------------------------------------------------------------------------------
-static bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 constexpr long long IF_MAX_GRID = (1LL << 31) - 1;
 
 static int if_shape(const char* who, const thz_ifta_desc* d, bool project, IfShape* s) {
@@ -339,13 +299,8 @@ static int if_shape(const char* who, const thz_ifta_desc* d, bool project, IfSha
 static size_t if_workspace(const IfShape& s) {
   return align256(sizeof(double) * IF_SUMS * (size_t)s.N * (size_t)s.chunks);
 }
-// 16-byte accesses: U (and out) and T 16-byte aligned, M 4-byte aligned, and every plane starting so
-static bool if_wide(const IfShape& s, std::initializer_list<const void*> p16, const void* m) {
-  if (s.HW % IF_PX && (s.N > 1 || s.t_planes > 1)) return false;
-  for (const void* p : p16)
-    if (misaligned(p, 16)) return false;
-  return !misaligned(m, 4);
-}
+// 16-byte accesses need U (and out) and T 16-byte aligned, M 4-byte aligned, and every plane starting so
+static bool if_planes16(const IfShape& s) { return s.HW % IF_PX == 0 || (s.N == 1 && s.t_planes == 1); }
 static int if_pointers(const char* who, const void* U, const float* T, const void* out) {
   if (!U || !T || !out) return fail(THZ_E_ARG, "%s: null pointer", who);
   if (misaligned(U, 4) || misaligned(T, 4)) return fail(THZ_E_ARG, "%s: array misaligned", who);
@@ -421,7 +376,7 @@ extern "C" int thz_ifta_target_stats(const thz_ifta_desc* d, const void* U, cons
   if (sh.chunks > 0) {  // H or W == 0: the finish kernel alone writes the empty statistics
     if (int e = if_pointers(who, U, T, out)) return e;
     if (int e = check_workspace(workspace, bytes, if_workspace(sh))) return e;
-    sh.wide = if_wide(sh, {U, T}, M);
+    sh.wide = if_planes16(sh) && all_aligned16({U, T}) && !misaligned(M, 4);
     const dim3 g((unsigned)(sh.N * sh.chunks));
     KernelTimer kt("ifta_target_stats", s);
     if (M) hipLaunchKernelGGL(ifta_stats_kernel<true>, g, b, 0, s, sh, (const float2*)U, T, M, (double*)workspace);
@@ -445,7 +400,7 @@ extern "C" int thz_ifta_target_project(const thz_ifta_desc* d, const void* U, co
   if (int e = if_pointers(who, U, T, out)) return e;
   if (!scale || misaligned(scale, sizeof(double))) return fail(THZ_E_ARG, "%s: scale null or misaligned", who);
   if (misaligned(out, 4)) return fail(THZ_E_ARG, "%s: array misaligned", who);
-  sh.wide = if_wide(sh, {U, T, out}, M);
+  sh.wide = if_planes16(sh) && all_aligned16({U, T, out}) && !misaligned(M, 4);
   hipStream_t s = (hipStream_t)stream;
   const dim3 g((unsigned)(sh.N * sh.chunks)), b(IF_THREADS);
   KernelTimer kt("ifta_target_project", s);

@@ -1,8 +1,11 @@
-// The host launch toolkit of the propagator units (thz_asm.hip, thz_rsc.hip, thz_czt.hip, thz_f64.hip):
-// the list of instantiated transform sizes and its dispatchers, workgroup sizes, the workspace
-// alignment and check, the large-LDS opt-in.  The noise unit (thz_noise.hip) takes the workspace
-// alignment and check from it.  Host code only; include after thz_common.hpp.
+// The host launch toolkit.  For the propagator units (thz_asm.hip, thz_rsc.hip, thz_czt.hip,
+// thz_f64.hip): the list of instantiated transform sizes and its dispatchers, workgroup sizes, the
+// large-LDS opt-in.  For every unit, the add-on units (noise, losses, heightmap, metrics, ifta,
+// optics) included: the workspace alignment and check and the pointer checks (misaligned,
+// check_arrays, all_aligned16).  Host code only; include after thz_common.hpp.
 #pragma once
+#include <cstdint>
+#include <initializer_list>
 #include <type_traits>
 #include <vector>
 
@@ -50,6 +53,25 @@ static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int check_workspace(const void* workspace, size_t bytes, size_t need) {
   if (!workspace || bytes < need) return fail(THZ_E_WORKSPACE, "workspace %zu bytes < required %zu", bytes, need);
   return THZ_OK;
+}
+
+// ---- pointer checks (host only, before any device call) --------------------------------------
+static bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+// every array present and aligned to its element
+static int check_arrays(const char* who, std::initializer_list<const void*> ptrs, size_t elem) {
+  for (const void* p : ptrs) {
+    if (!p) return fail(THZ_E_ARG, "%s: null pointer", who);
+    if (misaligned(p, elem)) return fail(THZ_E_ARG, "%s: array not %zu-byte aligned", who, elem);
+  }
+  return THZ_OK;
+}
+
+// the pointer half of a kernel's 16-byte form; a null pointer (an absent optional array) is aligned
+static bool all_aligned16(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (misaligned(p, 16)) return false;
+  return true;
 }
 
 // Workgroups above 64 KiB of dynamic LDS must opt in once per kernel.  Each kernel family keeps a

@@ -23,6 +23,7 @@
 
 #include "thz_common.hpp"
 #include "thz_dev.hpp"
+#include "thz_stream.hpp"
 #include "thz_launch.hpp"
 
 namespace thz {
@@ -69,30 +70,22 @@ __device__ __forceinline__ float bce_slope(float x, float t, float w, float pw) 
   return w * ((1.0f - t) - (1.0f + (pw - 1.0f) * t) * nsig);
 }
 
-// a lane's four consecutive values whether or not they move as one 16-byte access (thz_noise.hip):
-// a sum's bits then depend on the values only, not on the alignment of the arrays
-__device__ __forceinline__ PolLane<true> loss_sum_lane(long long c0, long long m, bool wide) {
-  PolLane<true> L(c0, m);
-  L.full = L.full && wide;
-  return L;
-}
-
-__device__ __forceinline__ void fill_ones(float v[POL_PX]) {
+__device__ __forceinline__ void fill_ones(float v[LANE_PX]) {
 #pragma unroll
-  for (int k = 0; k < POL_PX; ++k) v[k] = 1.0f;
+  for (int k = 0; k < LANE_PX; ++k) v[k] = 1.0f;
 }
 
 // partial[(n parts + part) 4 + k]: sample n's four sums over the chunks part, part + parts, ...
 template <int PK, bool WEIGHTED>
-__global__ void __launch_bounds__(POL_THREADS) dice_bce_sums_kernel(DiceBceArgs a, bool wide,
+__global__ void __launch_bounds__(LANE_THREADS) dice_bce_sums_kernel(DiceBceArgs a, bool wide,
                                                                     double* __restrict__ partial) {
   const long long n = blockIdx.x / a.parts, row = n * a.M;
   const int part = blockIdx.x % a.parts;
   const bool dice = a.terms & THZ_LOSS_TERM_DICE, bce = a.terms & THZ_LOSS_TERM_BCE;
   double s_pt = 0.0, s_pp = 0.0, s_tp = 0.0, s_b = 0.0;
-  for (long long c0 = (long long)part * POL_CHUNK; c0 < a.M; c0 += (long long)a.parts * POL_CHUNK) {
-    const PolLane<true> L = loss_sum_lane(c0, a.M, wide);
-    float x[POL_PX], t[POL_PX], w[POL_PX], pw[POL_PX], b[POL_PX];
+  for (long long c0 = (long long)part * LANE_CHUNK; c0 < a.M; c0 += (long long)a.parts * LANE_CHUNK) {
+    const Lane4<true> L = sum_lane(c0, a.M, wide);
+    float x[LANE_PX], t[LANE_PX], w[LANE_PX], pw[LANE_PX], b[LANE_PX];
     L.load(a.pred + row, x);
     L.load(a.target + row, t);
     fill_ones(w);
@@ -100,7 +93,7 @@ __global__ void __launch_bounds__(POL_THREADS) dice_bce_sums_kernel(DiceBceArgs 
     if (WEIGHTED && a.weight) L.load(a.weight + row, w);
     if (WEIGHTED && a.pos_weight) L.load(a.pos_weight + row, pw);
 #pragma unroll
-    for (int k = 0; k < POL_PX; ++k) {
+    for (int k = 0; k < LANE_PX; ++k) {
       b[k] = 0.0f;
       if (L.at(k) >= a.M) continue;
       if (dice) {
@@ -115,26 +108,15 @@ __global__ void __launch_bounds__(POL_THREADS) dice_bce_sums_kernel(DiceBceArgs 
     }
     if (a.map) L.store(a.map + row, b);
   }
-  s_pt = block_sum_fixed(s_pt);
-  s_pp = block_sum_fixed(s_pp);
-  s_tp = block_sum_fixed(s_tp);
-  s_b = block_sum_fixed(s_b);
-  if (threadIdx.x == 0) {
-    double* o = partial + (size_t)blockIdx.x * 4;
-    o[0] = s_pt; o[1] = s_pp; o[2] = s_tp; o[3] = s_b;
-  }
+  store_partials(Sums<4>{{s_pt, s_pp, s_tp, s_b}}, partial, blockIdx.x);
 }
 
 // sums[n][k] = the parts of sample n added in index order
-__global__ void __launch_bounds__(POL_THREADS) dice_bce_finish_kernel(const double* __restrict__ partial, int parts,
+__global__ void __launch_bounds__(LANE_THREADS) dice_bce_finish_kernel(const double* __restrict__ partial, int parts,
                                                                       double* __restrict__ sums) {
-  const double* p = partial + (size_t)blockIdx.x * parts * 4;
-  for (int k = 0; k < 4; ++k) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < parts; i += POL_THREADS) acc += p[(size_t)i * 4 + k];
-    acc = block_sum_fixed(acc);
-    if (threadIdx.x == 0) sums[(size_t)blockIdx.x * 4 + k] = acc;
-  }
+  const Sums<4> a = gather_partials<4>(partial, parts, (long long)blockIdx.x * parts);
+  if (threadIdx.x == 0)
+    for (int k = 0; k < 4; ++k) sums[(size_t)blockIdx.x * 4 + k] = a.v[k];
 }
 
 struct DiceBceGrads {
@@ -147,7 +129,7 @@ struct DiceBceGrads {
 
 // grad_pred = g_dice[n] d/dp (1 - num / den) + g_bce d/dp bce
 template <int PK, bool WEIGHTED, bool WIDE>
-__global__ void __launch_bounds__(POL_THREADS) dice_bce_bwd_kernel(DiceBceArgs a, DiceBceGrads g,
+__global__ void __launch_bounds__(LANE_THREADS) dice_bce_bwd_kernel(DiceBceArgs a, DiceBceGrads g,
                                                                    float* __restrict__ grad) {
   const long long n = blockIdx.x / a.parts, row = n * a.M;
   const int part = blockIdx.x % a.parts;
@@ -160,9 +142,9 @@ __global__ void __launch_bounds__(POL_THREADS) dice_bce_bwd_kernel(DiceBceArgs a
     cp = (float)(gd * num / (den * den));
   }
   if (bce && !g.elementwise) gb = *g.g_bce;
-  for (long long c0 = (long long)part * POL_CHUNK; c0 < a.M; c0 += (long long)a.parts * POL_CHUNK) {
-    const PolLane<WIDE> L(c0, a.M);
-    float x[POL_PX], t[POL_PX], w[POL_PX], pw[POL_PX], ge[POL_PX], out[POL_PX];
+  for (long long c0 = (long long)part * LANE_CHUNK; c0 < a.M; c0 += (long long)a.parts * LANE_CHUNK) {
+    const Lane4<WIDE> L(c0, a.M);
+    float x[LANE_PX], t[LANE_PX], w[LANE_PX], pw[LANE_PX], ge[LANE_PX], out[LANE_PX];
     L.load(a.pred + row, x);
     L.load(a.target + row, t);
     fill_ones(w);
@@ -171,7 +153,7 @@ __global__ void __launch_bounds__(POL_THREADS) dice_bce_bwd_kernel(DiceBceArgs a
     if (WEIGHTED && a.pos_weight) L.load(a.pos_weight + row, pw);
     if (bce && g.elementwise) L.load(g.g_bce + row, ge);
 #pragma unroll
-    for (int k = 0; k < POL_PX; ++k) {
+    for (int k = 0; k < LANE_PX; ++k) {
       float v = 0.0f;
       if (L.at(k) < a.M) {
         if (dice) v = ct * t[k] + cp * dice_dpow<PK>(x[k], a.p);
@@ -301,29 +283,19 @@ __global__ void __launch_bounds__(SS_THREADS) ssim_fwd_kernel(SsimArgs a, const 
       o3[2 * cstride] = (float)(2.0 * A1 * ib12);
     }
   }
-  sum_s = block_sum_fixed(sum_s);
-  sum_cs = block_sum_fixed(sum_cs);
-  if (tid == 0) {
-    const size_t tiles = (size_t)gridDim.x * gridDim.y, tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    partial[(plane * tiles + tile) * 2] = sum_s;
-    partial[(plane * tiles + tile) * 2 + 1] = sum_cs;
-  }
+  const long long tiles = (long long)gridDim.x * gridDim.y, tile = (long long)blockIdx.y * gridDim.x + blockIdx.x;
+  store_partials(Sums<2>{{sum_s, sum_cs}}, partial, plane * tiles + tile);
 }
 
 // ssim[plane], cs[plane] = the means over the window positions; nonnegative: relu on ssim
-__global__ void __launch_bounds__(POL_THREADS) ssim_finish_kernel(const double* __restrict__ partial, int tiles,
+__global__ void __launch_bounds__(LANE_THREADS) ssim_finish_kernel(const double* __restrict__ partial, int tiles,
                                                                   double positions, int nonnegative,
                                                                   float* __restrict__ ssim, float* __restrict__ cs) {
-  const double* p = partial + (size_t)blockIdx.x * tiles * 2;
-  for (int k = 0; k < 2; ++k) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < tiles; i += POL_THREADS) acc += p[(size_t)i * 2 + k];
-    acc = block_sum_fixed(acc);
-    if (threadIdx.x == 0) {
-      const float m = (float)(acc / positions);
-      if (k == 0) ssim[blockIdx.x] = nonnegative ? fmaxf(m, 0.0f) : m;
-      else if (cs) cs[blockIdx.x] = m;
-    }
+  const Sums<2> a = gather_partials<2>(partial, tiles, (long long)blockIdx.x * tiles);
+  if (threadIdx.x == 0) {
+    const float ms = (float)(a.v[0] / positions), mc = (float)(a.v[1] / positions);
+    ssim[blockIdx.x] = nonnegative ? fmaxf(ms, 0.0f) : ms;
+    if (cs) cs[blockIdx.x] = mc;
   }
 }
 
@@ -417,17 +389,6 @@ __global__ void __launch_bounds__(SS_THREADS) ssim_bwd_kernel(SsimArgs a, const 
 }
 
 // ---- host side -------------------------------------------------------------------------------
-static bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-static int check_ptrs(const char* who, std::initializer_list<const void*> ptrs, size_t elem) {
-  for (const void* p : ptrs) {
-    if (!p) return fail(THZ_E_ARG, "%s: null pointer", who);
-    if (misaligned(p, elem)) return fail(THZ_E_ARG, "%s: array not %zu-byte aligned", who, elem);
-  }
-  return THZ_OK;
-}
-
-constexpr int LOSS_MAX_PARTS = 1024;        // workgroups of a partial-sum launch (4 per CU on an MI355X)
 constexpr long long LOSS_MAX_N = 1LL << 24;  // samples: N parts stays far inside a grid's x extent
 
 static int dice_bce_check(const char* who, const thz_dice_bce_desc* d) {
@@ -443,26 +404,18 @@ static int dice_bce_check(const char* who, const thz_dice_bce_desc* d) {
 
 // a grid that depends on (N, M) alone, so a sum's bits depend on the values only
 static int dice_bce_parts(const thz_dice_bce_desc* d) {
-  const long long chunks = (d->M + POL_CHUNK - 1) / POL_CHUNK;
-  const long long cap = d->N >= LOSS_MAX_PARTS ? 1 : LOSS_MAX_PARTS / d->N;
-  return (int)(chunks < cap ? chunks : cap);
+  return partial_parts((d->M + LANE_CHUNK - 1) / LANE_CHUNK, d->N);
 }
 static size_t dice_bce_workspace(const thz_dice_bce_desc* d) {
   return align256(sizeof(double) * 4 * (size_t)d->N * dice_bce_parts(d));
 }
 static int dice_pk(float p) { return p == 1.0f ? 1 : p == 2.0f ? 2 : 0; }
 
-static bool loss_wide(std::initializer_list<const void*> ptrs, long long m) {
-  bool wide = m % POL_PX == 0;
-  for (const void* p : ptrs) wide = wide && !misaligned(p, 16);  // a null pointer is aligned
-  return wide;
-}
-
 template <int PK, bool WEIGHTED>
 static void dice_bce_bwd_launch(bool wide, dim3 g, hipStream_t s, const DiceBceArgs& a, const DiceBceGrads& gr,
                                 float* grad) {
-  if (wide) hipLaunchKernelGGL((dice_bce_bwd_kernel<PK, WEIGHTED, true>), g, dim3(POL_THREADS), 0, s, a, gr, grad);
-  else hipLaunchKernelGGL((dice_bce_bwd_kernel<PK, WEIGHTED, false>), g, dim3(POL_THREADS), 0, s, a, gr, grad);
+  if (wide) hipLaunchKernelGGL((dice_bce_bwd_kernel<PK, WEIGHTED, true>), g, dim3(LANE_THREADS), 0, s, a, gr, grad);
+  else hipLaunchKernelGGL((dice_bce_bwd_kernel<PK, WEIGHTED, false>), g, dim3(LANE_THREADS), 0, s, a, gr, grad);
 }
 
 // pk in {0, 1, 2} and weighted as compile-time values: f(Size<PK>{}, std::bool_constant<WEIGHTED>{})
@@ -541,17 +494,17 @@ extern "C" int thz_dice_bce_sums(const thz_dice_bce_desc* d, const float* pred, 
                                  float* bce_map, void* workspace, size_t bytes, thz_stream_t stream) {
   const char* who = "thz_dice_bce_sums";
   if (int e = dice_bce_check(who, d)) return e;
-  if (int e = check_ptrs(who, {pred, target}, sizeof(float))) return e;
-  if (int e = check_ptrs(who, {sums, workspace}, sizeof(double))) return e;
+  if (int e = check_arrays(who, {pred, target}, sizeof(float))) return e;
+  if (int e = check_arrays(who, {sums, workspace}, sizeof(double))) return e;
   if (bce_map && misaligned(bce_map, sizeof(float))) return fail(THZ_E_ARG, "%s: bce_map misaligned", who);
   if (bce_map && !(d->terms & THZ_LOSS_TERM_BCE)) return fail(THZ_E_ARG, "%s: bce_map without the BCE term", who);
   if (int e = check_workspace(workspace, bytes, dice_bce_workspace(d))) return e;
   hipStream_t s = (hipStream_t)stream;
   const int parts = dice_bce_parts(d);
   const DiceBceArgs a{pred, target, d->weight, d->pos_weight, bce_map, d->M, parts, d->terms, d->p};
-  const bool wide = loss_wide({pred, target, d->weight, d->pos_weight, bce_map}, d->M);
+  const bool wide = d->M % LANE_PX == 0 && all_aligned16({pred, target, d->weight, d->pos_weight, bce_map});
   double* partial = (double*)workspace;
-  const dim3 g((unsigned)(d->N * parts)), b(POL_THREADS);
+  const dim3 g((unsigned)(d->N * parts)), b(LANE_THREADS);
   KernelTimer kp("dice_bce_sums", s);
   on_dice_kind(dice_pk(d->p), d->weight || d->pos_weight, [&](auto PK, auto WEIGHTED) {
     hipLaunchKernelGGL((dice_bce_sums_kernel<PK(), WEIGHTED()>), g, b, 0, s, a, wide, partial);
@@ -570,19 +523,20 @@ extern "C" int thz_dice_bce_backward(const thz_dice_bce_desc* d, const float* pr
                                      thz_stream_t stream) {
   const char* who = "thz_dice_bce_backward";
   if (int e = dice_bce_check(who, d)) return e;
-  if (int e = check_ptrs(who, {pred, target, grad_pred}, sizeof(float))) return e;
+  if (int e = check_arrays(who, {pred, target, grad_pred}, sizeof(float))) return e;
   if (d->terms & THZ_LOSS_TERM_DICE) {
-    if (int e = check_ptrs(who, {sums}, sizeof(double))) return e;
-    if (int e = check_ptrs(who, {g_dice}, sizeof(float))) return e;
+    if (int e = check_arrays(who, {sums}, sizeof(double))) return e;
+    if (int e = check_arrays(who, {g_dice}, sizeof(float))) return e;
   }
   if (d->terms & THZ_LOSS_TERM_BCE)
-    if (int e = check_ptrs(who, {g_bce}, sizeof(float))) return e;
+    if (int e = check_arrays(who, {g_bce}, sizeof(float))) return e;
   hipStream_t s = (hipStream_t)stream;
   const int parts = dice_bce_parts(d);
   const DiceBceArgs a{pred, target, d->weight, d->pos_weight, nullptr, d->M, parts, d->terms, d->p};
   const DiceBceGrads gr{sums, g_dice, g_bce, d->bce_grad_elementwise, d->smooth};
-  const bool wide = loss_wide({pred, target, d->weight, d->pos_weight, grad_pred,
-                               d->bce_grad_elementwise && (d->terms & THZ_LOSS_TERM_BCE) ? g_bce : nullptr}, d->M);
+  const bool wide = d->M % LANE_PX == 0 &&
+                    all_aligned16({pred, target, d->weight, d->pos_weight, grad_pred,
+                                   d->bce_grad_elementwise && (d->terms & THZ_LOSS_TERM_BCE) ? g_bce : nullptr});
   const dim3 g((unsigned)(d->N * parts));
   KernelTimer kt("dice_bce_bwd", s);
   on_dice_kind(dice_pk(d->p), d->weight || d->pos_weight, [&](auto PK, auto WEIGHTED) {
@@ -605,8 +559,8 @@ extern "C" int thz_ssim_forward(const thz_ssim_desc* d, const float* x, const fl
                                 float* coef, void* workspace, size_t bytes, thz_stream_t stream) {
   const char* who = "thz_ssim_forward";
   if (int e = ssim_check(who, d)) return e;
-  if (int e = check_ptrs(who, {x, y, ssim}, sizeof(float))) return e;
-  if (int e = check_ptrs(who, {workspace}, sizeof(double))) return e;
+  if (int e = check_arrays(who, {x, y, ssim}, sizeof(float))) return e;
+  if (int e = check_arrays(who, {workspace}, sizeof(double))) return e;
   for (const void* p : {(const void*)cs, (const void*)coef})
     if (p && misaligned(p, sizeof(float))) return fail(THZ_E_ARG, "%s: output misaligned", who);
   const SsimArgs a = ssim_args(d);
@@ -620,7 +574,7 @@ extern "C" int thz_ssim_forward(const thz_ssim_desc* d, const float* x, const fl
   THZ_LAUNCH_CHECK();
   kt.stop();
   KernelTimer kf("ssim_finish", s);
-  hipLaunchKernelGGL(ssim_finish_kernel, dim3((unsigned)d->NC), dim3(POL_THREADS), 0, s, (const double*)partial,
+  hipLaunchKernelGGL(ssim_finish_kernel, dim3((unsigned)d->NC), dim3(LANE_THREADS), 0, s, (const double*)partial,
                      (int)(g.x * g.y), (double)a.Ho * (double)a.Wo, a.nonnegative, ssim, cs);
   THZ_LAUNCH_CHECK();
   kf.stop();
@@ -631,7 +585,7 @@ extern "C" int thz_ssim_backward(const thz_ssim_desc* d, const float* x, const f
                                  const float* ssim, const float* g, float* grad_x, thz_stream_t stream) {
   const char* who = "thz_ssim_backward";
   if (int e = ssim_check(who, d)) return e;
-  if (int e = check_ptrs(who, {x, y, coef, ssim, g, grad_x}, sizeof(float))) return e;
+  if (int e = check_arrays(who, {x, y, coef, ssim, g, grad_x}, sizeof(float))) return e;
   const SsimArgs a = ssim_args(d);
   if (int e = ssim_lds_attr()) return e;
   hipStream_t s = (hipStream_t)stream;

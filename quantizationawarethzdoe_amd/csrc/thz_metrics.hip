@@ -10,7 +10,7 @@
 //                              of each), holds its 32 intensities in registers and visits only the regions
 //                              whose bounding box meets the tile, so an element is read once however many
 //                              regions there are.  The workgroup's result per region goes to the workspace
-//                              (block_merge, the struct form of block_sum_fixed); region_stats_finish_kernel
+//                              (block_reduce_fixed on the whole struct); region_stats_finish_kernel
 //                              merges a plane's tiles in index order.  No atomics: the same input gives the
 //                              same bits.
 //   thz_region_stats_backward  one pass on the same tiles: grad_I = sum over the regions that hold the
@@ -26,6 +26,7 @@
 
 #include "thz_common.hpp"
 #include "thz_dev.hpp"
+#include "thz_stream.hpp"
 #include "thz_launch.hpp"
 
 namespace thz {
@@ -152,34 +153,11 @@ __device__ __forceinline__ double2 rs_scale(double2 v, double g) { return make_d
 // the lane's four elements of row i (i < H), zero past the row's end
 template <class T>
 __device__ __forceinline__ void rs_load(const T* __restrict__ p, const RsShape& s, const RsTile& t, int i, T v[RS_PX]) {
-  const T* row = p + t.plane + (long long)i * s.W;
-  if (s.wide && t.c0 + (RS_PX - 1) < s.W) {
-    constexpr int NQ = (int)(sizeof(T) * RS_PX / 16);
-    uint4 raw[NQ];
-    const uint4* q = reinterpret_cast<const uint4*>(row + t.c0);
-#pragma unroll
-    for (int m = 0; m < NQ; ++m) raw[m] = q[m];
-    __builtin_memcpy(v, raw, sizeof(raw));
-  } else {
-#pragma unroll
-    for (int k = 0; k < RS_PX; ++k) v[k] = t.c0 + k < s.W ? row[t.c0 + k] : T{};
-  }
+  ld4(p + t.plane + (long long)i * s.W, t.c0, s.W, s.wide, v);
 }
 template <class T>
 __device__ __forceinline__ void rs_store(T* __restrict__ p, const RsShape& s, const RsTile& t, int i, const T v[RS_PX]) {
-  T* row = p + t.plane + (long long)i * s.W;
-  if (s.wide && t.c0 + (RS_PX - 1) < s.W) {
-    constexpr int NQ = (int)(sizeof(T) * RS_PX / 16);
-    uint4 raw[NQ];
-    __builtin_memcpy(raw, v, sizeof(raw));
-    uint4* q = reinterpret_cast<uint4*>(row + t.c0);
-#pragma unroll
-    for (int m = 0; m < NQ; ++m) q[m] = raw[m];
-  } else {
-#pragma unroll
-    for (int k = 0; k < RS_PX; ++k)
-      if (t.c0 + k < s.W) row[t.c0 + k] = v[k];
-  }
+  st4(p + t.plane + (long long)i * s.W, t.c0, s.W, s.wide, v);
 }
 
 // the statistics of one region over some pixels
@@ -212,6 +190,13 @@ struct RsAcc {
       arg = o.arg;
     }
   }
+  __device__ __forceinline__ RsAcc shfl_xor(int o) const {  // for block_reduce_fixed
+    RsAcc b;
+    b.s0 = __shfl_xor(s0, o); b.sr = __shfl_xor(sr, o); b.sc = __shfl_xor(sc, o);
+    b.srr = __shfl_xor(srr, o); b.scc = __shfl_xor(scc, o); b.peak = __shfl_xor(peak, o);
+    b.cnt = __shfl_xor(cnt, o); b.arg = __shfl_xor(arg, o);
+    return b;
+  }
   __device__ __forceinline__ void store(double* o) const {
     const bool any = cnt > 0.0;
     o[0] = s0; o[1] = sr; o[2] = sc; o[3] = srr; o[4] = scc;
@@ -229,26 +214,6 @@ struct RsAcc {
     return a;
   }
 };
-
-// block_sum_fixed for the whole struct: xor butterfly inside a wave, then the waves in index order;
-// valid in thread 0.  Every thread of the workgroup must call it.
-__device__ __forceinline__ RsAcc block_merge(RsAcc a) {
-  __shared__ RsAcc s_w[16];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    RsAcc b;
-    b.s0 = __shfl_xor(a.s0, o); b.sr = __shfl_xor(a.sr, o); b.sc = __shfl_xor(a.sc, o);
-    b.srr = __shfl_xor(a.srr, o); b.scc = __shfl_xor(a.scc, o); b.peak = __shfl_xor(a.peak, o);
-    b.cnt = __shfl_xor(a.cnt, o); b.arg = __shfl_xor(a.arg, o);
-    a.merge(b);
-  }
-  __syncthreads();
-  if (lane == 0) s_w[wid] = a;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < nw; ++w) a.merge(s_w[w]);
-  return a;
-}
 
 // is pixel (i, j) inside?  dii = (i - cr)^2 for a circle, |i - cr| for a rectangle; djj alike
 __device__ __forceinline__ bool rs_member(const RsBox& x, double dii, double djj, double aa) {
@@ -314,13 +279,13 @@ __global__ void __launch_bounds__(RS_THREADS) RS_OCC region_stats_fwd_kernel(RsS
       }
       if (loc >= 0) acc.arg = (long long)(r0 + loc / RS_PX) * s.W + (c0 + loc % RS_PX);
     }
-    acc = block_merge(acc);
+    acc = block_reduce_fixed(acc);
     if (threadIdx.x == 0) acc.store(partial + ((size_t)t.slot * (s.K + 1) + k) * RS_STATS);
   }
 }
 
 // out[(n (K + 1) + k) 8 ..]: one workgroup per plane and region merges the plane's tiles, each thread
-// its tiles in ascending order, then block_merge
+// its tiles in ascending order (gather_reduce)
 __global__ void __launch_bounds__(RS_THREADS) region_stats_finish_kernel(RsShape s, RsTable tab,
                                                                          const double* __restrict__ partial,
                                                                          double* __restrict__ out) {
@@ -330,12 +295,11 @@ __global__ void __launch_bounds__(RS_THREADS) region_stats_finish_kernel(RsShape
   const long long per = (long long)s.tx * s.ty;
   RsAcc acc;
   acc.clear();
-  for (long long tile = threadIdx.x; tile < per; tile += RS_THREADS) {
+  acc = gather_reduce(acc, per, [&](long long tile, RsAcc& a) {
     const int R0 = (int)(tile / s.tx) * RS_ROWS, C0 = (int)(tile % s.tx) * RS_COLS;
-    if (!rs_hits(b, R0, R0 + RS_ROWS - 1, C0, C0 + RS_COLS - 1)) continue;
-    acc.merge(RsAcc::of(partial + ((size_t)(n * per + tile) * (s.K + 1) + k) * RS_STATS));
-  }
-  acc = block_merge(acc);
+    if (!rs_hits(b, R0, R0 + RS_ROWS - 1, C0, C0 + RS_COLS - 1)) return;
+    a.merge(RsAcc::of(partial + ((size_t)(n * per + tile) * (s.K + 1) + k) * RS_STATS));
+  });
   if (threadIdx.x == 0) acc.store(out + (size_t)blockIdx.x * RS_STATS);
 }
 
@@ -493,8 +457,6 @@ __global__ void __launch_bounds__(LW_THREADS) line_widths_kernel(const T* __rest
 #pragma clang fp contract(on)
 
 // ---- host side -------------------------------------------------------------------------------
-static bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 static size_t elem_bytes(int dtype) {
   switch (dtype) {
     case THZ_METRICS_C64: return 8;
@@ -543,12 +505,8 @@ static long long rs_tiles(const RsShape& s) { return s.N * s.tx * s.ty; }
 static size_t rs_workspace(const RsShape& s) {
   return align256(sizeof(double) * RS_STATS * (size_t)(s.K + 1) * (size_t)rs_tiles(s));
 }
-static bool rs_wide(const RsShape& s, int dtype, std::initializer_list<const void*> ptrs) {
-  if (((size_t)s.W * elem_bytes(dtype)) % 16) return false;
-  for (const void* p : ptrs)
-    if (misaligned(p, 16)) return false;
-  return true;
-}
+// every row starts 16-byte aligned when the base pointers do
+static bool rs_pitch16(const RsShape& s, int dtype) { return ((size_t)s.W * elem_bytes(dtype)) % 16 == 0; }
 
 // f(T{}) with the element type of dtype
 template <class F>
@@ -589,7 +547,7 @@ extern "C" int thz_region_stats_forward(const thz_region_stats_desc* d, const vo
   if (rs_tiles(sh) > 0) {  // H or W == 0: no pixel, the finish kernel alone writes the empty statistics
     if (!x || misaligned(x, comp_bytes(d->dtype))) return fail(THZ_E_ARG, "%s: x null or misaligned", who);
     if (int e = check_workspace(workspace, bytes, rs_workspace(sh))) return e;
-    sh.wide = rs_wide(sh, d->dtype, {x});
+    sh.wide = rs_pitch16(sh, d->dtype) && all_aligned16({x});
     KernelTimer kt("region_stats_fwd", s);
     on_dtype(d->dtype, [&](auto T) {
       using E = decltype(T);
@@ -619,7 +577,7 @@ extern "C" int thz_region_stats_backward(const thz_region_stats_desc* d, const v
   if (!G || !grad) return fail(THZ_E_ARG, "%s: null pointer", who);
   if (misaligned(x, comp_bytes(d->dtype)) || misaligned(grad, comp_bytes(d->dtype)) || misaligned(G, sizeof(double)))
     return fail(THZ_E_ARG, "%s: array misaligned", who);
-  sh.wide = field ? rs_wide(sh, d->dtype, {x, grad}) : rs_wide(sh, d->dtype, {grad});
+  sh.wide = rs_pitch16(sh, d->dtype) && all_aligned16({field ? x : nullptr, grad});
   hipStream_t s = (hipStream_t)stream;
   KernelTimer kt("region_stats_bwd", s);
   on_dtype(d->dtype, [&](auto T) {

@@ -1,11 +1,11 @@
 // Detector noise models (Addons/Noise.py:4-112, utils/Noise.py:4-116, utils/Helper_Functions.py:
-// 258-366) on the counter-based device generator (thz_dev.hpp: rng_bits and the samplers built on it).
+// 258-366) on the counter-based device generator (thz_dev.hpp: rng_bits; the samplers built on it are here).
 //
 //   thz_noise_apply         one streaming pass: reads the measurement (or the complex64 field, whose
 //                           |E|^2 it forms in registers) and writes the noisy one -- 12 B per pixel for
 //                           a field, 8 B for an intensity, against the ~60 B of the reference's seven
 //                           elementwise passes and two RNG kernels.  The streaming lane of the Stokes
-//                           kernels (PolLane): 16-byte accesses when the pointers and n allow, else the
+//                           kernels (Lane4): 16-byte accesses when the pointers and n allow, else the
 //                           same body at element width; the arithmetic is per element and this unit
 //                           compiles with contraction off, so both forms and every grid give the same bits.
 //   thz_noise_draws         the raw draws of the same (state, stream, index), for tests.
@@ -20,11 +20,116 @@
 
 #include "thz_common.hpp"
 #include "thz_dev.hpp"
+#include "thz_stream.hpp"
 #include "thz_launch.hpp"
 
 #pragma clang fp contract(off)
 
 namespace thz {
+
+// ---------------------------------------------------------------------------------------------
+// Detector-noise samplers (Addons/Noise.py:27,58,87-89, utils/Noise.py:32) on the counter-based
+// generator of thz_dev.hpp: pure functions of (rng state, stream, element index, parameters), so a
+// forward and its backward regenerate the same draw and a result never depends on the launch geometry
+// or on what a neighbouring lane does.  fp32, contraction off.
+// ---------------------------------------------------------------------------------------------
+// Two independent standard normals from one rng_bits word (torch.randn): Box-Muller on two 24-bit
+// uniforms, r = sqrt(-2 log u1) with u1 = (b1 + 1) / 2^24 in (0, 1] as in rng_exp1 (log(0) cannot
+// occur), angle u2 = b2 / 2^24 in [0, 1) revolutions -- the unit of v_sin_f32 / v_cos_f32 -- giving
+// (r cos, r sin).  The smallest u1 bounds |n| by sqrt(2 * 24 * ln 2) = 5.768 (the normal mass beyond
+// it is 8e-9).  A real draw takes .x; a complex draw takes both.
+__device__ __forceinline__ float2 rng_normal2(const unsigned* rng, unsigned stream, unsigned idx) {
+  const unsigned long long w = rng_bits(rng, stream, idx);
+  const float u1 = (float)((unsigned)(w >> 40) + 1u) * (1.0f / 16777216.0f);
+  const float u2 = (float)((unsigned)(w >> 16) & 0xFFFFFFu) * (1.0f / 16777216.0f);
+  const float r = sqrtf(-2.0f * logf(u1));
+  return make_float2(r * __builtin_amdgcn_cosf(u2), r * __builtin_amdgcn_sinf(u2));
+}
+__device__ __forceinline__ float rng_normal(const unsigned* rng, unsigned stream, unsigned idx) {
+  return rng_normal2(rng, stream, idx).x;
+}
+// complex standard normal, variance 1 in total (torch.randn of a complex dtype: 1/2 per component)
+__device__ __forceinline__ float2 rng_cnormal(const unsigned* rng, unsigned stream, unsigned idx) {
+  const float2 z = rng_normal2(rng, stream, idx);
+  return make_float2(z.x * 0.70710678118654752f, z.y * 0.70710678118654752f);
+}
+
+// Poisson(lam) (torch.poisson), returned as a float.  lam = 0 gives 0; lam < 0 or NaN gives NaN (no
+// host check: that would be a sync).  Rates up to 2^24 are supported (beyond it fp32 no longer holds
+// every count); the tests cover 0.05 to 1e5.
+//
+// Attempt j of element idx draws word j of a splitmix64 sequence of its own, seeded with the
+// element's base word rng_bits(state, stream ^ "POIS", idx): w_j = mix(base + (j + 1) gamma).  The
+// attempt number enters the 64-bit counter in a hash round of its own and never the 32-bit stream,
+// so (stream, j) pairs cannot alias: two streams' attempt sequences start from two hashed 64-bit
+// words and meet only if those differ by a small multiple of gamma (probability ~2^-60 per pair).
+// No w_j is the base word itself, so the Poisson draws of a stream are also apart from its normal /
+// uniform draws, and a lane's sample does not depend on how long its neighbours loop.
+//
+// lam < 10: inversion by sequential search in fp64 on a 53-bit uniform (a 24-bit uniform could not
+// reach the tail mass below 2^-24).  P(X >= 64 | lam < 10) < 4e-30, far below the uniform's 2^-53
+// resolution, so the search bound of 64 only stops a cumulative sum that rounding left below u.
+//
+// lam >= 10: Hoermann's transformed rejection with squeeze (PTRS, Insurance: Mathematics and
+// Economics 12 (1993) 39-45; the algorithm of numpy and of torch's CPU poisson), fp32.  U has 23
+// bits and is centred ((b + 1/2) / 2^23 - 1/2, never 0 or +-1/2), V = (b + 1) / 2^24 in (0, 1].  An
+// attempt accepts with probability 1 / invalpha: 0.75 at lam = 10, above 0.85 from lam = 90, 0.89
+// in the limit; the squeeze alone (no log, no lgamma) accepts 0.35 - 0.80.  The loop runs until the
+// lane accepts: there is no attempt cap, since returning early would bias the sample.
+//
+// The acceptance test compares with log pmf(k) = -lam + k log lam - lgamma(k + 1)
+// (rng_poisson_logpmf).  Evaluated as written, with lgammaf, its terms are ~lam log lam and cancel
+// to a few units: the result would carry 1e-3 absolute at lam = 1000 and 0.1 at 1e5.  So that form
+// serves k < 16 only (small terms, or a candidate so far below lam that it is rejected whatever the
+// rounding); from k = 16 Stirling's series for lgamma is folded in analytically, with d = k - lam
+// and t = d / lam,
+//   log pmf = -d t + k (t - log1p(t)) - log(2 pi k) / 2 - 1 / (12 k) + 1 / (360 k^3)   (+ < 1e-9),
+// whose terms are of the size of d: ~1e-5 absolute at lam = 1000, ~1e-4 at 1e5.
+constexpr unsigned RNG_POISSON_STREAM = 0x504F4953u;  // "POIS"
+__device__ __forceinline__ unsigned long long rng_poisson_word(unsigned long long base, unsigned attempt) {
+  unsigned long long x = base + ((unsigned long long)attempt + 1ull) * 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+__device__ __forceinline__ float rng_poisson_logpmf(float k, float lam, float loglam) {
+  if (k < 16.0f) return -lam + k * loglam - lgammaf(k + 1.0f);
+  const float d = k - lam, t = d / lam, ik = 1.0f / k;
+  return (-d * t + k * (t - log1pf(t))) - 0.5f * logf(6.2831853071795865f * k) -
+         ik * (0.083333333333333333f - 0.0027777777777777778f * ik * ik);
+}
+__device__ inline float rng_poisson(const unsigned* rng, unsigned stream, unsigned idx, float lam) {
+  if (!(lam >= 0.0f)) return __builtin_nanf("");
+  if (lam == 0.0f) return 0.0f;
+  const unsigned long long base = rng_bits(rng, stream ^ RNG_POISSON_STREAM, idx);
+  if (lam < 10.0f) {
+    const double u = (double)(rng_poisson_word(base, 0u) >> 11) * 0x1p-53;
+    const double l = (double)lam;
+    double p = exp(-l), s = p;
+    int k = 0;
+    while (u >= s && k < 64) {
+      ++k;
+      p *= l / (double)k;
+      s += p;
+    }
+    return (float)k;
+  }
+  const float slam = sqrtf(lam), loglam = logf(lam);
+  const float b = 0.931f + 2.53f * slam;
+  const float a = -0.059f + 0.02483f * b;
+  const float invalpha = 1.1239f + 1.1328f / (b - 3.4f);
+  const float vr = 0.9277f - 3.6224f / (b - 2.0f);
+  for (unsigned j = 0u;; ++j) {
+    const unsigned long long w = rng_poisson_word(base, j);
+    const float U = ((float)(unsigned)(w >> 41) + 0.5f) * (1.0f / 8388608.0f) - 0.5f;
+    const float V = (float)(((unsigned)(w >> 16) & 0xFFFFFFu) + 1u) * (1.0f / 16777216.0f);
+    const float us = 0.5f - fabsf(U);
+    const float k = floorf((2.0f * a / us + b) * U + lam + 0.43f);
+    if (us >= 0.07f && V <= vr) return k;
+    if (k < 0.0f || (us < 0.013f && V > us)) continue;
+    if (logf(V) + logf(invalpha) - logf(a / (us * us) + b) <= rng_poisson_logpmf(k, lam, loglam)) return k;
+  }
+}
 
 struct NoiseArgs {
   float sigma, a, gain;
@@ -45,43 +150,43 @@ __device__ __forceinline__ float noise_model(float x, unsigned idx, const NoiseA
 }
 
 template <int KIND, int INPUT, bool WIDE>
-__global__ void __launch_bounds__(POL_THREADS) noise_apply_kernel(const void* __restrict__ in, void* __restrict__ out,
+__global__ void __launch_bounds__(LANE_THREADS) noise_apply_kernel(const void* __restrict__ in, void* __restrict__ out,
                                                                   long long n, NoiseArgs p) {
   const float sigma = p.sigma_dev ? *p.sigma_dev : p.sigma;
-  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < n; c0 += (long long)gridDim.x * POL_CHUNK) {
-    const PolLane<WIDE> L(c0, n);
+  for (long long c0 = (long long)blockIdx.x * LANE_CHUNK; c0 < n; c0 += (long long)gridDim.x * LANE_CHUNK) {
+    const Lane4<WIDE> L(c0, n);
     if (INPUT == THZ_NOISE_IN_COMPLEX64) {
-      float2 v[POL_PX];
+      float2 v[LANE_PX];
       L.load((const float2*)in, v);
 #pragma unroll
-      for (int k = 0; k < POL_PX; ++k) {
+      for (int k = 0; k < LANE_PX; ++k) {
         if (L.at(k) >= n) continue;
         const float2 z = rng_cnormal(p.rng, p.stream, (unsigned)L.at(k));
         v[k] = make_float2(v[k].x + z.x * sigma, v[k].y + z.y * sigma);
       }
       L.store((float2*)out, v);
     } else {
-      float x[POL_PX];
+      float x[LANE_PX];
       if (INPUT == THZ_NOISE_IN_FIELD_INTENSITY) {
-        float2 e[POL_PX];
+        float2 e[LANE_PX];
         L.load((const float2*)in, e);
 #pragma unroll
-        for (int k = 0; k < POL_PX; ++k) x[k] = loss_intensity(e[k]);  // field.abs() ** 2
+        for (int k = 0; k < LANE_PX; ++k) x[k] = loss_intensity(e[k]);  // field.abs() ** 2
       } else {
         L.load((const float*)in, x);
       }
 #pragma unroll
-      for (int k = 0; k < POL_PX; ++k)
+      for (int k = 0; k < LANE_PX; ++k)
         if (L.at(k) < n) x[k] = noise_model<KIND>(x[k], (unsigned)L.at(k), p, sigma);
       L.store((float*)out, x);
     }
   }
 }
 
-__global__ void __launch_bounds__(POL_THREADS) noise_draws_kernel(int what, const unsigned* __restrict__ rng,
+__global__ void __launch_bounds__(LANE_THREADS) noise_draws_kernel(int what, const unsigned* __restrict__ rng,
                                                                   unsigned stream, long long n,
                                                                   float* __restrict__ out) {
-  for (long long i = (long long)blockIdx.x * POL_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * POL_THREADS) {
+  for (long long i = (long long)blockIdx.x * LANE_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * LANE_THREADS) {
     if (what == THZ_DRAW_NORMAL) {
       out[i] = rng_normal(rng, stream, (unsigned)i);
     } else if (what == THZ_DRAW_UNIFORM) {
@@ -94,67 +199,48 @@ __global__ void __launch_bounds__(POL_THREADS) noise_draws_kernel(int what, cons
   }
 }
 
-// ---- the two-stage fp64 sums -----------------------------------------------------------------
-constexpr int SUM_MAX_PARTS = 1024;  // workgroups of a partial-sum launch (4 per CU on an MI355X)
-static int sum_parts(long long elems) {
-  const long long chunks = (elems + POL_CHUNK - 1) / POL_CHUNK;
-  return (int)(chunks < SUM_MAX_PARTS ? chunks : SUM_MAX_PARTS);
-}
+// ---- the two-stage fp64 sums (thz_stream.hpp) ------------------------------------------------
+static int sum_parts(long long elems) { return partial_parts((elems + LANE_CHUNK - 1) / LANE_CHUNK); }
 // workspace: the partials, then the backward's coefficient (one float in its own 256 bytes)
-static size_t sum_coef_offset() { return align256(sizeof(double) * SUM_MAX_PARTS); }
+static size_t sum_coef_offset() { return align256(sizeof(double) * MAX_PARTS); }
 static size_t sum_workspace_bytes() { return sum_coef_offset() + 256; }
 
-// a lane's four consecutive values of a float array: one 16-byte load when `wide` (16-byte aligned
-// base, whole group inside m), else four bound-checked loads -- the same values in the same lane
-__device__ __forceinline__ PolLane<true> sum_lane(long long c0, long long m, bool wide) {
-  PolLane<true> L(c0, m);
-  L.full = L.full && wide;
-  return L;
-}
-
 // partial[b] = sum over workgroup b's chunks of x_f^2, f over m floats (a complex array is its 2 n floats)
-__global__ void __launch_bounds__(POL_THREADS) signal_scale_part_kernel(const float* __restrict__ x, long long m,
+__global__ void __launch_bounds__(LANE_THREADS) signal_scale_part_kernel(const float* __restrict__ x, long long m,
                                                                         bool wide, double* __restrict__ partial) {
   double acc = 0.0;
-  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < m; c0 += (long long)gridDim.x * POL_CHUNK) {
-    const PolLane<true> L = sum_lane(c0, m, wide);
-    float v[POL_PX];
+  for (long long c0 = (long long)blockIdx.x * LANE_CHUNK; c0 < m; c0 += (long long)gridDim.x * LANE_CHUNK) {
+    const Lane4<true> L = sum_lane(c0, m, wide);
+    float v[LANE_PX];
     L.load(x, v);
 #pragma unroll
-    for (int k = 0; k < POL_PX; ++k) acc += (double)v[k] * (double)v[k];
+    for (int k = 0; k < LANE_PX; ++k) acc += (double)v[k] * (double)v[k];
   }
-  acc = block_sum_fixed(acc);
-  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-
-__device__ __forceinline__ double sum_partials(const double* __restrict__ partial, int parts) {
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < parts; i += POL_THREADS) acc += partial[i];
-  return block_sum_fixed(acc);
+  store_partials(Sums<1>{{acc}}, partial, blockIdx.x);
 }
 
 // scale = sqrt(mean |x|^2 / snr) (utils/Noise.py:28-32), rounded to fp32 once
-__global__ void __launch_bounds__(POL_THREADS) signal_scale_finish_kernel(const double* __restrict__ partial, int parts,
+__global__ void __launch_bounds__(LANE_THREADS) signal_scale_finish_kernel(const double* __restrict__ partial, int parts,
                                                                           double n, double snr,
                                                                           float* __restrict__ scale) {
-  const double sum = sum_partials(partial, parts);
+  const double sum = gather_partials<1>(partial, parts).v[0];
   if (threadIdx.x == 0) *scale = (float)sqrt(sum / n / snr);
 }
 
 // partial[b] = sum of Re(conj(g_i) n_i) over workgroup b's chunks; n_i regenerated from (rng, stream, i).
 // Real: a lane owns elements 4 t .. 4 t + 3 of its chunk; complex: the floats of elements 2 t, 2 t + 1.
 template <bool CPLX>
-__global__ void __launch_bounds__(POL_THREADS) snr_noise_bwd_part_kernel(const float* __restrict__ g, long long m,
+__global__ void __launch_bounds__(LANE_THREADS) snr_noise_bwd_part_kernel(const float* __restrict__ g, long long m,
                                                                          bool wide, const unsigned* __restrict__ rng,
                                                                          unsigned stream, double* __restrict__ partial) {
   double acc = 0.0;
-  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < m; c0 += (long long)gridDim.x * POL_CHUNK) {
-    const PolLane<true> L = sum_lane(c0, m, wide);
-    float v[POL_PX];
+  for (long long c0 = (long long)blockIdx.x * LANE_CHUNK; c0 < m; c0 += (long long)gridDim.x * LANE_CHUNK) {
+    const Lane4<true> L = sum_lane(c0, m, wide);
+    float v[LANE_PX];
     L.load(g, v);
     if (CPLX) {
 #pragma unroll
-      for (int k = 0; k < POL_PX; k += 2) {
+      for (int k = 0; k < LANE_PX; k += 2) {
         if (L.at(k) >= m) continue;
         const float2 z = rng_cnormal(rng, stream, (unsigned)(L.at(k) >> 1));
         acc += (double)v[k] * (double)z.x;
@@ -162,68 +248,56 @@ __global__ void __launch_bounds__(POL_THREADS) snr_noise_bwd_part_kernel(const f
       }
     } else {
 #pragma unroll
-      for (int k = 0; k < POL_PX; ++k)
+      for (int k = 0; k < LANE_PX; ++k)
         if (L.at(k) < m) acc += (double)v[k] * (double)rng_normal(rng, stream, (unsigned)L.at(k));
     }
   }
-  acc = block_sum_fixed(acc);
-  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+  store_partials(Sums<1>{{acc}}, partial, blockIdx.x);
 }
 
 // coef = S / (N snr scale), rounded to fp32 once
-__global__ void __launch_bounds__(POL_THREADS) snr_noise_bwd_finish_kernel(const double* __restrict__ partial,
+__global__ void __launch_bounds__(LANE_THREADS) snr_noise_bwd_finish_kernel(const double* __restrict__ partial,
                                                                            int parts, double n, double snr,
                                                                            const float* __restrict__ scale,
                                                                            float* __restrict__ coef) {
-  const double sum = sum_partials(partial, parts);
+  const double sum = gather_partials<1>(partial, parts).v[0];
   if (threadIdx.x == 0) *coef = (float)(sum / (n * snr * (double)*scale));
 }
 
 // gx = g + x coef over m floats
 template <bool WIDE>
-__global__ void __launch_bounds__(POL_THREADS) snr_noise_bwd_kernel(const float* __restrict__ g,
+__global__ void __launch_bounds__(LANE_THREADS) snr_noise_bwd_kernel(const float* __restrict__ g,
                                                                     const float* __restrict__ x, long long m,
                                                                     const float* __restrict__ coef,
                                                                     float* __restrict__ gx) {
   const float c = *coef;
-  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < m; c0 += (long long)gridDim.x * POL_CHUNK) {
-    const PolLane<WIDE> L(c0, m);
-    float gv[POL_PX], xv[POL_PX];
+  for (long long c0 = (long long)blockIdx.x * LANE_CHUNK; c0 < m; c0 += (long long)gridDim.x * LANE_CHUNK) {
+    const Lane4<WIDE> L(c0, m);
+    float gv[LANE_PX], xv[LANE_PX];
     L.load(g, gv);
     L.load(x, xv);
 #pragma unroll
-    for (int k = 0; k < POL_PX; ++k) gv[k] = gv[k] + xv[k] * c;
+    for (int k = 0; k < LANE_PX; ++k) gv[k] = gv[k] + xv[k] * c;
     L.store(gx, gv);
   }
 }
 
 // ---- host side -------------------------------------------------------------------------------
-static bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 constexpr long long NOISE_MAX_N = 1LL << 32;  // the generator's element index is 32-bit
 
-// null, alignment and range checks shared by the entries (host only, before any device call)
+// the arrays, then the range of n, shared by the entries
 static int noise_check(const char* who, std::initializer_list<const void*> ptrs, size_t elem, long long n) {
-  for (const void* p : ptrs) {
-    if (!p) return fail(THZ_E_ARG, "%s: null pointer", who);
-    if (misaligned(p, elem)) return fail(THZ_E_ARG, "%s: array not %zu-byte aligned", who, elem);
-  }
+  if (int e = check_arrays(who, ptrs, elem)) return e;
   if (n < 0) return fail(THZ_E_ARG, "%s: n = %lld < 0", who, n);
   if (n > NOISE_MAX_N) return fail(THZ_E_ARG, "%s: n = %lld > 2^32, the generator's index range", who, n);
   return THZ_OK;
 }
 
-static bool all_wide(std::initializer_list<const void*> ptrs, long long elems) {
-  bool wide = elems % POL_PX == 0;
-  for (const void* p : ptrs) wide = wide && !misaligned(p, 16);
-  return wide;
-}
-
 template <int KIND, int INPUT>
 static void noise_apply_launch(bool wide, dim3 g, hipStream_t s, const void* in, void* out, long long n,
                                const NoiseArgs& p) {
-  if (wide) hipLaunchKernelGGL((noise_apply_kernel<KIND, INPUT, true>), g, dim3(POL_THREADS), 0, s, in, out, n, p);
-  else hipLaunchKernelGGL((noise_apply_kernel<KIND, INPUT, false>), g, dim3(POL_THREADS), 0, s, in, out, n, p);
+  if (wide) hipLaunchKernelGGL((noise_apply_kernel<KIND, INPUT, true>), g, dim3(LANE_THREADS), 0, s, in, out, n, p);
+  else hipLaunchKernelGGL((noise_apply_kernel<KIND, INPUT, false>), g, dim3(LANE_THREADS), 0, s, in, out, n, p);
 }
 
 template <int INPUT>
@@ -259,9 +333,9 @@ extern "C" int thz_noise_apply(const thz_noise_desc* d, const void* in, void* ou
   if (n == 0) return THZ_OK;
   hipStream_t s = (hipStream_t)stream;
   int blocks = 0;
-  if (int e = stream_grid((n + POL_CHUNK - 1) / POL_CHUNK, &blocks)) return e;
+  if (int e = stream_grid((n + LANE_CHUNK - 1) / LANE_CHUNK, &blocks)) return e;
   const NoiseArgs p{d->sigma, d->a, d->gain, d->normalize, d->sigma_dev, d->rng, d->stream};
-  const bool wide = all_wide({in, out}, n);
+  const bool wide = n % LANE_PX == 0 && all_aligned16({in, out});
   KernelTimer kt("noise_apply", s);
   const dim3 g((unsigned)blocks);
   if (d->input == THZ_NOISE_IN_COMPLEX64) noise_apply_launch<THZ_NOISE_GAUSS, THZ_NOISE_IN_COMPLEX64>(wide, g, s, in, out, n, p);
@@ -280,9 +354,9 @@ extern "C" int thz_noise_draws(int what, const unsigned* rng, unsigned stream, l
   if (n == 0) return THZ_OK;
   hipStream_t s = (hipStream_t)stream_handle;
   int blocks = 0;
-  if (int e = stream_grid((n + POL_THREADS - 1) / POL_THREADS, &blocks)) return e;
+  if (int e = stream_grid((n + LANE_THREADS - 1) / LANE_THREADS, &blocks)) return e;
   KernelTimer kt("noise_draws", s);
-  hipLaunchKernelGGL(noise_draws_kernel, dim3((unsigned)blocks), dim3(POL_THREADS), 0, s, what, rng, stream, n, out);
+  hipLaunchKernelGGL(noise_draws_kernel, dim3((unsigned)blocks), dim3(LANE_THREADS), 0, s, what, rng, stream, n, out);
   THZ_LAUNCH_CHECK();
   kt.stop();
   return THZ_OK;
@@ -309,12 +383,12 @@ extern "C" int thz_signal_scale(const void* x, long long n, int is_complex, floa
   const int parts = sum_parts(m);
   double* partial = (double*)workspace;
   KernelTimer kp("signal_scale_part", s);
-  hipLaunchKernelGGL(signal_scale_part_kernel, dim3((unsigned)parts), dim3(POL_THREADS), 0, s, (const float*)x, m,
-                     all_wide({x}, m), partial);
+  hipLaunchKernelGGL(signal_scale_part_kernel, dim3((unsigned)parts), dim3(LANE_THREADS), 0, s, (const float*)x, m,
+                     m % LANE_PX == 0 && all_aligned16({x}), partial);
   THZ_LAUNCH_CHECK();
   kp.stop();
   KernelTimer kf("signal_scale_finish", s);
-  hipLaunchKernelGGL(signal_scale_finish_kernel, dim3(1), dim3(POL_THREADS), 0, s, (const double*)partial, parts,
+  hipLaunchKernelGGL(signal_scale_finish_kernel, dim3(1), dim3(LANE_THREADS), 0, s, (const double*)partial, parts,
                      (double)n, (double)snr_linear, scale);
   THZ_LAUNCH_CHECK();
   kf.stop();
@@ -336,14 +410,13 @@ extern "C" int thz_snr_noise_backward(const void* g, const void* x, long long n,
   const int parts = sum_parts(m);
   double* partial = (double*)workspace;
   float* coef = (float*)((char*)workspace + sum_coef_offset());
-  const dim3 pg((unsigned)parts), b(POL_THREADS);
+  const dim3 pg((unsigned)parts), b(LANE_THREADS);
+  const bool gwide = m % LANE_PX == 0 && all_aligned16({g});
   KernelTimer kp("snr_noise_bwd_part", s);
   if (is_complex)
-    hipLaunchKernelGGL(snr_noise_bwd_part_kernel<true>, pg, b, 0, s, (const float*)g, m, all_wide({g}, m), rng, stream,
-                       partial);
+    hipLaunchKernelGGL(snr_noise_bwd_part_kernel<true>, pg, b, 0, s, (const float*)g, m, gwide, rng, stream, partial);
   else
-    hipLaunchKernelGGL(snr_noise_bwd_part_kernel<false>, pg, b, 0, s, (const float*)g, m, all_wide({g}, m), rng, stream,
-                       partial);
+    hipLaunchKernelGGL(snr_noise_bwd_part_kernel<false>, pg, b, 0, s, (const float*)g, m, gwide, rng, stream, partial);
   THZ_LAUNCH_CHECK();
   kp.stop();
   KernelTimer kf("snr_noise_bwd_finish", s);
@@ -352,9 +425,9 @@ extern "C" int thz_snr_noise_backward(const void* g, const void* x, long long n,
   THZ_LAUNCH_CHECK();
   kf.stop();
   int blocks = 0;
-  if (int e = stream_grid((m + POL_CHUNK - 1) / POL_CHUNK, &blocks)) return e;
+  if (int e = stream_grid((m + LANE_CHUNK - 1) / LANE_CHUNK, &blocks)) return e;
   KernelTimer ka("snr_noise_bwd", s);
-  if (all_wide({g, x, gx}, m))
+  if (gwide && all_aligned16({x, gx}))
     hipLaunchKernelGGL(snr_noise_bwd_kernel<true>, dim3((unsigned)blocks), b, 0, s, (const float*)g, (const float*)x, m,
                        (const float*)coef, (float*)gx);
   else

@@ -17,6 +17,8 @@
 
 #include "thz_common.hpp"
 #include "thz_dev.hpp"
+#include "thz_stream.hpp"
+#include "thz_launch.hpp"
 
 #pragma clang fp contract(off)
 
@@ -432,7 +434,7 @@ __global__ void __launch_bounds__(64) step_fetch_kernel(const int* ring, int dep
 // Polarization analysis of a vectorial field (Addons/Polarization.py:45-92): the Stokes vector, its
 // backward and the ellipse parameters, one streaming pass each over the Ex and Ey planes (the Ez
 // plane is never read).  Memory-bound: 16 B read and 16 B written per pixel (backward: 32 + 16).
-// The kernels run on the streaming lane of thz_dev.hpp (PolLane, POL_THREADS / POL_PX / POL_CHUNK,
+// The kernels run on the streaming lane of thz_stream.hpp (Lane4, LANE_THREADS / LANE_PX / LANE_CHUNK,
 // described there and shared with thz_noise.hip): two 16-byte loads per component and one 16-byte
 // store per output plane in the wide form, which pol_check picks only when every pointer is 16-byte
 // aligned and n % 4 == 0 (the Ey plane of a contiguous [3, C, H, W] tensor with an odd plane starts
@@ -451,17 +453,17 @@ __device__ __forceinline__ StokesPx stokes_px(float2 x, float2 y) {
 }
 
 template <bool WIDE>
-__global__ void __launch_bounds__(POL_THREADS) stokes_fwd_kernel(const float2* __restrict__ ex,
+__global__ void __launch_bounds__(LANE_THREADS) stokes_fwd_kernel(const float2* __restrict__ ex,
                                                                  const float2* __restrict__ ey, long long n,
                                                                  float* __restrict__ out) {
-  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < n; c0 += (long long)gridDim.x * POL_CHUNK) {
-    const PolLane<WIDE> L(c0, n);
-    float2 x[POL_PX], y[POL_PX];
+  for (long long c0 = (long long)blockIdx.x * LANE_CHUNK; c0 < n; c0 += (long long)gridDim.x * LANE_CHUNK) {
+    const Lane4<WIDE> L(c0, n);
+    float2 x[LANE_PX], y[LANE_PX];
     L.load(ex, x);
     L.load(ey, y);
-    float o[4][POL_PX];
+    float o[4][LANE_PX];
 #pragma unroll
-    for (int k = 0; k < POL_PX; ++k) {
+    for (int k = 0; k < LANE_PX; ++k) {
       const StokesPx s = stokes_px(x[k], y[k]);
       o[0][k] = s.I; o[1][k] = s.Q; o[2][k] = s.U; o[3][k] = s.V;
     }
@@ -475,20 +477,20 @@ __global__ void __launch_bounds__(POL_THREADS) stokes_fwd_kernel(const float2* _
 // dI = 2 Ey, dQ = -2 Ey, dU = 2 Ex, dV = 2 (b - ia) = -2i Ex towards Ey, so
 //   gEx = 2 [(gI + gQ) Ex + (gU + i gV) Ey],   gEy = 2 [(gI - gQ) Ey + (gU - i gV) Ex]
 template <bool WIDE>
-__global__ void __launch_bounds__(POL_THREADS) stokes_bwd_kernel(const float2* __restrict__ ex,
+__global__ void __launch_bounds__(LANE_THREADS) stokes_bwd_kernel(const float2* __restrict__ ex,
                                                                  const float2* __restrict__ ey, long long n,
                                                                  const float* __restrict__ g,
                                                                  float2* __restrict__ gex, float2* __restrict__ gey) {
-  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < n; c0 += (long long)gridDim.x * POL_CHUNK) {
-    const PolLane<WIDE> L(c0, n);
-    float2 x[POL_PX], y[POL_PX], gx[POL_PX], gy[POL_PX];
-    float gs[4][POL_PX];
+  for (long long c0 = (long long)blockIdx.x * LANE_CHUNK; c0 < n; c0 += (long long)gridDim.x * LANE_CHUNK) {
+    const Lane4<WIDE> L(c0, n);
+    float2 x[LANE_PX], y[LANE_PX], gx[LANE_PX], gy[LANE_PX];
+    float gs[4][LANE_PX];
     L.load(ex, x);
     L.load(ey, y);
 #pragma unroll
     for (int q = 0; q < 4; ++q) L.load(g + q * n, gs[q]);
 #pragma unroll
-    for (int k = 0; k < POL_PX; ++k) {
+    for (int k = 0; k < LANE_PX; ++k) {
       const float sa = gs[0][k] + gs[1][k], sb = gs[0][k] - gs[1][k], gU = gs[2][k], gV = gs[3][k];
       gx[k] = make_float2(2.f * (sa * x[k].x + (gU * y[k].x - gV * y[k].y)),
                           2.f * (sa * x[k].y + (gU * y[k].y + gV * y[k].x)));
@@ -517,38 +519,35 @@ __device__ __forceinline__ void ellipse_px(float2 x, float2 y, float* A, float* 
 }
 
 template <bool WIDE>
-__global__ void __launch_bounds__(POL_THREADS) polarization_ellipse_kernel(const float2* __restrict__ ex,
+__global__ void __launch_bounds__(LANE_THREADS) polarization_ellipse_kernel(const float2* __restrict__ ex,
                                                                            const float2* __restrict__ ey,
                                                                            long long n, float* __restrict__ out) {
-  for (long long c0 = (long long)blockIdx.x * POL_CHUNK; c0 < n; c0 += (long long)gridDim.x * POL_CHUNK) {
-    const PolLane<WIDE> L(c0, n);
-    float2 x[POL_PX], y[POL_PX];
+  for (long long c0 = (long long)blockIdx.x * LANE_CHUNK; c0 < n; c0 += (long long)gridDim.x * LANE_CHUNK) {
+    const Lane4<WIDE> L(c0, n);
+    float2 x[LANE_PX], y[LANE_PX];
     L.load(ex, x);
     L.load(ey, y);
-    float o[4][POL_PX];
+    float o[4][LANE_PX];
 #pragma unroll
-    for (int k = 0; k < POL_PX; ++k) ellipse_px(x[k], y[k], &o[0][k], &o[1][k], &o[2][k], &o[3][k]);
+    for (int k = 0; k < LANE_PX; ++k) ellipse_px(x[k], y[k], &o[0][k], &o[1][k], &o[2][k], &o[3][k]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) L.store(out + q * n, o[q]);
   }
 }
 
-static bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 // host validation shared by the polarization entries: cplx are complex64 planes, real float planes
 static int pol_check(const char* who, std::initializer_list<const void*> cplx, std::initializer_list<const void*> real,
                      long long n, bool* wide) {
-  *wide = n % POL_PX == 0;
   for (const void* p : cplx) {
     if (!p) return fail(THZ_E_ARG, "%s: null pointer", who);
     if (misaligned(p, sizeof(float2))) return fail(THZ_E_ARG, "%s: complex plane not 8-byte aligned", who);
-    *wide = *wide && !misaligned(p, 16);
   }
   for (const void* p : real) {
     if (!p) return fail(THZ_E_ARG, "%s: null pointer", who);
     if (misaligned(p, sizeof(float))) return fail(THZ_E_ARG, "%s: real plane not 4-byte aligned", who);
-    *wide = *wide && !misaligned(p, 16);  // with n % 4 == 0 planes 1-3 are aligned as plane 0 is
   }
+  // with n % 4 == 0 planes 1-3 of a real array are aligned as plane 0 is
+  *wide = n % LANE_PX == 0 && all_aligned16(cplx) && all_aligned16(real);
   if (n < 0) return fail(THZ_E_ARG, "%s: n = %lld < 0", who, n);
   return THZ_OK;
 }
@@ -798,9 +797,9 @@ template <class Launch>
 static int pol_launch(const char* timer, long long n, hipStream_t s, Launch&& launch) {
   if (n == 0) return THZ_OK;
   int blocks = 0;
-  if (int e = stream_grid((n + POL_CHUNK - 1) / POL_CHUNK, &blocks)) return e;
+  if (int e = stream_grid((n + LANE_CHUNK - 1) / LANE_CHUNK, &blocks)) return e;
   KernelTimer kt(timer, s);
-  launch(dim3((unsigned)blocks), dim3(POL_THREADS));
+  launch(dim3((unsigned)blocks), dim3(LANE_THREADS));
   THZ_LAUNCH_CHECK();
   kt.stop();
   return THZ_OK;
