@@ -1063,6 +1063,70 @@ int thz_ifta_doe_project(const thz_ifta_doe_desc* d, const void* U, const void* 
                          thz_stream_t stream);
 
 /*
+ * Full-wave validator: a 3-D Yee-grid FDTD solver for one dielectric relief on air (thz_fdtd.hip;
+ * quantizationawarethzdoe_amd/fdtd.py -- the reference sends its designs to external solvers).  Additive:
+ * THZ_ABI_VERSION stays 9, a caller detects the entries by symbol.
+ *
+ * Cubic cells of side delta, axes (z, y, x) with x fastest; y and x are the height map's H and W and are
+ * periodic, z is the optical axis (the wave travels toward +z) and ends in npml cells of CPML on both sides.
+ * Nx = W ppc and Ny = H ppc with ppc = pixel / delta a whole number; for H = 1 any Ny >= 1 is legal (the
+ * y-invariant problem; Ny = 1 is the 2-D problem exactly).  Units inside: c = 1, lengths in cells, H times
+ * eta0, dt = courant cells.  The six fields are float32 [Nz][Ny][Nx]; all cell indexing is 64-bit.
+ *
+ * The element starts at plane k_elem: n_base cells of base plate, then per pixel floor(clamp(h, 0,
+ * thickness) / delta + 1/2) cells of relief (element = 0: no dielectric, the normalisation run).  The host
+ * hands over three tables, formed once in fp64 by the caller (fdtd.py; tests/fdtd_ref.py states them):
+ *   step_table [n_table][5] fp64   per step: the source's cos and sin times its ramp (float32 values), the
+ *                                  DFT's cos and sin, and whether the step is accumulated (non-zero)
+ *   cpml [8][npml] float32         (b, c) at the E planes and (b, c) at the H planes of the front slab (plane
+ *                                  l), then of the back slab (plane Nz - npml + l)
+ *   cacb [10] float32              Ca[n], Cb[n] for n = 0 .. 4 dielectric cells of the four around an edge
+ * A current sheet on plane k_src drives Ex (polarization 0) or Ey (1) with 2 courant (Re A cos + Im A sin),
+ * A the complex64 [H, W] incident amplitude on the pixel grid (NULL: 1).  The running DFT of Ex, Ey, Ez is
+ * summed in fp64, in time order, on n_planes (<= THZ_FDTD_MAX_PLANES) transverse planes plane_k[], on the
+ * x-z slice of row `row` and on the y-z slice of column `col` (-1: none).  A device step counter in the
+ * workspace selects the table's row; steps past n_table run without source and without accumulation.
+ *
+ * thz_fdtd_setup      rasterises, clears fields, psi, accumulators and the counter, copies the tables
+ * thz_fdtd_run        enqueues 2 n_steps launches (H pass, E pass); no host sync, capturable
+ * thz_fdtd_monitors   the accumulators times 2 / n_acc as complex64: planes_out [n_planes][3][Ny][Nx],
+ *                     zx_out [3][Nz][Nx], zy_out [3][Nz][Ny]
+ * thz_fdtd_fields     out6 [6][Nz][Ny][Nx]: Ex, Ey, Ez, Hx, Hy, Hz as they stand (a hook for tests)
+ * thz_fdtd_material   out [Nz][Ny][Nx] uint16: the rasterised word nx | ny << 3 | nz << 6 of edge counts (a hook
+ *                     for tests: the rasteriser against the restatement; no product code calls it)
+ * Every entry checks before any device call: a null descriptor, pointer or table, a misaligned array, a bad
+ * shape, a Courant number outside (0, 1 / sqrt(3)], the source plane, a monitor plane or the element inside
+ * a PML slab are THZ_E_ARG; a pixel that is no whole number of cells and a grid beyond the launch extent
+ * are THZ_E_UNSUPPORTED; a workspace (256-byte aligned) below thz_fdtd_workspace_size is THZ_E_WORKSPACE.
+ */
+#define THZ_FDTD_MAX_PLANES 8
+typedef struct thz_fdtd_desc {
+  int Nz, Ny, Nx;                /* cells */
+  int H, W;                      /* pixels of the height map */
+  double pixel, delta, courant;
+  int npml, k_elem, n_base, element;
+  float thickness;
+  int k_src, polarization;
+  int n_planes;
+  int plane_k[THZ_FDTD_MAX_PLANES];
+  int row, col;
+  long long n_table;
+  int n_acc;                     /* accumulated steps: the monitors' scale is 2 / n_acc */
+  const double* step_table;      /* host */
+  const float* cpml;             /* host */
+  const float* cacb;             /* host */
+} thz_fdtd_desc;
+int thz_fdtd_workspace_size(const thz_fdtd_desc* d, size_t* bytes);
+int thz_fdtd_setup(const thz_fdtd_desc* d, const float* height, const void* incident, void* workspace, size_t bytes,
+                   thz_stream_t stream);
+int thz_fdtd_run(const thz_fdtd_desc* d, void* workspace, size_t bytes, long long n_steps, thz_stream_t stream);
+int thz_fdtd_monitors(const thz_fdtd_desc* d, const void* workspace, size_t bytes, void* planes_out, void* zx_out,
+                      void* zy_out, thz_stream_t stream);
+int thz_fdtd_fields(const thz_fdtd_desc* d, const void* workspace, size_t bytes, float* out6, thz_stream_t stream);
+int thz_fdtd_material(const thz_fdtd_desc* d, const void* workspace, size_t bytes, unsigned short* out,
+                      thz_stream_t stream);
+
+/*
  * Batched 1-D FFT along the contiguous axis (the building block of ft2/ift2,
  * utils/Helper_Functions.py:150, without shifts): in/out [rows, n], unnormalised,
  * inverse != 0 for the backward transform.  n <= 16384, any factorisation.

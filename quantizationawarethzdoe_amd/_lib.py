@@ -55,6 +55,8 @@ EXPORTED = [
     "thz_tv_workspace_size", "thz_tv_forward", "thz_tv_backward",
     "thz_region_stats_workspace_size", "thz_region_stats_forward", "thz_region_stats_backward", "thz_line_widths",
     "thz_ifta_target_stats_workspace_size", "thz_ifta_target_stats", "thz_ifta_target_project", "thz_ifta_doe_project",
+    "thz_fdtd_workspace_size", "thz_fdtd_setup", "thz_fdtd_run", "thz_fdtd_monitors", "thz_fdtd_fields",
+    "thz_fdtd_material",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -308,6 +310,23 @@ class IftaDoeDesc(ctypes.Structure):
                 ("L", ctypes.c_int), ("lut", ctypes.c_float * THZ_MAX_LUT)]
 
 
+THZ_FDTD_MAX_PLANES = 8
+
+
+class FdtdDesc(ctypes.Structure):
+    _fields_ = [("Nz", ctypes.c_int), ("Ny", ctypes.c_int), ("Nx", ctypes.c_int),
+                ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("pixel", ctypes.c_double), ("delta", ctypes.c_double), ("courant", ctypes.c_double),
+                ("npml", ctypes.c_int), ("k_elem", ctypes.c_int), ("n_base", ctypes.c_int), ("element", ctypes.c_int),
+                ("thickness", ctypes.c_float), ("k_src", ctypes.c_int), ("polarization", ctypes.c_int),
+                ("n_planes", ctypes.c_int), ("plane_k", ctypes.c_int * THZ_FDTD_MAX_PLANES),
+                ("row", ctypes.c_int), ("col", ctypes.c_int),
+                ("n_table", ctypes.c_longlong), ("n_acc", ctypes.c_int),
+                ("step_table", ctypes.c_void_p),  # const double* host [n_table][5]
+                ("cpml", ctypes.c_void_p),        # const float* host [8][npml]
+                ("cacb", ctypes.c_void_p)]        # const float* host [10]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -421,6 +440,13 @@ def _declare(lib):
                                             c_void_p]
     lib.thz_ifta_doe_project.argtypes = [ctypes.POINTER(IftaDoeDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]
+    fd = ctypes.POINTER(FdtdDesc)
+    lib.thz_fdtd_workspace_size.argtypes = [fd, ctypes.POINTER(c_size_t)]
+    lib.thz_fdtd_setup.argtypes = [fd, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_fdtd_run.argtypes = [fd, c_void_p, c_size_t, c_ll, c_void_p]
+    lib.thz_fdtd_monitors.argtypes = [fd, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.thz_fdtd_fields.argtypes = [fd, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.thz_fdtd_material.argtypes = [fd, c_void_p, c_size_t, c_void_p, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,
