@@ -1127,6 +1127,75 @@ int thz_fdtd_material(const thz_fdtd_desc* d, const void* workspace, size_t byte
                       thz_stream_t stream);
 
 /*
+ * Fabrication-tolerance Monte Carlo: K perturbed realisations of one height map applied to one incident
+ * field in one streaming pass (thz_tolerance.hip; quantizationawarethzdoe_amd/tolerance.py).  Additive:
+ * THZ_ABI_VERSION stays 9, a caller detects the entries by symbol.  The reference has one term of this
+ * model, add_height_map_noise's per-pixel U(-tol, tol) draw (Components/QuantizedDOE.py:82-87).
+ *
+ * For realisation k (absolute index, first <= k < first + K) and pixel p of the [hs, ws] map with level
+ * index l = idx[p], in fp32, in this operation order, contraction off:
+ *   u_k[p] = ((1 + g_k) * h[p] + e_{k,l}) + r_k[p]
+ *   h_k[p] = min(max(u_k[p], lo), hi)
+ *   out[k, c, q] = field[b, c, q] * t_c(h_k[src(q)])      b = 0 for Bf == 1, else k - first
+ *   g_k     = sigma_scale * n(THZ_TOL_TAG_SCALE, k)                  a depth-scale error
+ *   e_{k,l} = sigma_level[l] * n(THZ_TOL_TAG_LEVEL, 16 k + l)        a per-level depth error; an idx value
+ *                                                                    outside 0 .. L-1 takes none
+ *   r_k[p]  = ((u - 0.5) * 2) * rough   (THZ_TOL_ROUGH_UNIFORM, the reference's formula)
+ *           = rough * n                 (THZ_TOL_ROUGH_NORMAL), drawn at (THZ_TOL_TAG_ROUGH, k hs ws + p)
+ * n is thz_noise_draws' THZ_DRAW_NORMAL and u its THZ_DRAW_UNIFORM of (rng, stream ^ tag, index).  A term
+ * whose sigma is 0 is not drawn and contributes +0.  t_c is the transmission of thz_doe_modulate_forward
+ * (base plate included), src its nearest upsampling, and the complex product is that kernel's, so
+ * out[k] == thz_doe_modulate_forward(field, heights_out[k]) bit for bit.  A realisation is a pure function
+ * of (seed, step, stream, k, p): it does not depend on first (how K is chunked), on the field size, on the
+ * launch geometry or on whether the 16-byte path ran (all pointers 16-byte aligned and H W % 4 == 0) or the
+ * element-width one.
+ *
+ * field [Bf, C, H, W] complex64 with Bf = 1 or K; height [hs, ws] float32; idx [hs, ws] int32 or NULL (legal
+ * only when every sigma_level is 0); out [K, C, H, W] complex64; heights_out [K, hs, ws] float32 or NULL.
+ *
+ * thz_tolerance_modulate_backward, for the cotangent G = grad_out [K, C, H, W], every draw regenerated:
+ *   grad_height[p] = sum_k (1 + g_k) [lo < u_k[p] < hi] sum_c sum_{q: src(q) = p}
+ *                    Re(conj(G[k,c,q]) field[b,c,q] t_c(h_k[p]) gamma_c)              float32 [hs, ws], or NULL
+ *   grad_field     = G conj(t), summed over k when Bf == 1                          complex64 [Bf, C, H, W], or NULL
+ * One thread owns a map pixel and the field pixels that read it, and sums in fp64 in the fixed order
+ * (c, q row-major, k): no atomics, the same bits from every call and every grid.  It needs no workspace
+ * today (workspace may be NULL and bytes 0; the parameters are reserved).
+ *
+ * Checked on the host before any device call: null pointers, a shape below 1, Bf other than 1 or K, L outside
+ * 0 .. THZ_MAX_LUT, a negative or NaN sigma or roughness, an unknown roughness kind, lo > hi or a NaN bound,
+ * first < 0, (first + K) hs ws > 2^32 or (first + K) 16 > 2^32 (the generator's index is 32-bit), idx == NULL
+ * with a non-zero sigma_level, and misaligned arrays are THZ_E_ARG; C > THZ_MAX_WAVELENGTHS is
+ * THZ_E_UNSUPPORTED.
+ */
+#define THZ_TOL_TAG_SCALE 0x5343414Cu /* "SCAL" */
+#define THZ_TOL_TAG_LEVEL 0x4C45564Cu /* "LEVL" */
+#define THZ_TOL_TAG_ROUGH 0x524F5547u /* "ROUG" */
+#define THZ_TOL_ROUGH_NONE 0
+#define THZ_TOL_ROUGH_UNIFORM 1
+#define THZ_TOL_ROUGH_NORMAL 2
+typedef struct thz_tolerance_desc {
+  int K;                     /* realisations of this call */
+  long long first;           /* absolute index of the first */
+  int Bf;                    /* batch items of field: 1 or K */
+  int C, H, W, hs, ws;
+  int L;                     /* entries of sigma_level, 0 .. THZ_MAX_LUT */
+  float sigma_level[THZ_MAX_LUT];
+  float sigma_scale;
+  int rough_kind;            /* THZ_TOL_ROUGH_* */
+  float rough;
+  float lo, hi;              /* clamp; -inf / +inf switch a side off */
+  float epsilon, tand;
+  const float* wavelengths;  /* host [C] */
+  const unsigned* rng;       /* device [2] = {seed, step} */
+  unsigned stream;
+} thz_tolerance_desc;
+int thz_tolerance_modulate_forward(const thz_tolerance_desc* d, const void* field, const float* height, const int* idx,
+                                   void* out, float* heights_out, thz_stream_t stream);
+int thz_tolerance_modulate_backward(const thz_tolerance_desc* d, const void* grad_out, const void* field,
+                                    const float* height, const int* idx, void* grad_field, float* grad_height,
+                                    void* workspace, size_t bytes, thz_stream_t stream);
+
+/*
  * Batched 1-D FFT along the contiguous axis (the building block of ft2/ift2,
  * utils/Helper_Functions.py:150, without shifts): in/out [rows, n], unnormalised,
  * inverse != 0 for the backward transform.  n <= 16384, any factorisation.
@@ -1246,7 +1315,8 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * "snr_noise_bwd"; the loss entries: "dice_bce_sums", "dice_bce_finish", "dice_bce_bwd", "ssim_fwd",
  * "ssim_finish", "ssim_bwd"; the height-map entries: "lut_quantize_fwd", "lut_quantize_bwd", "center_difference",
  * "tv_fwd", "tv_finish", "tv_bwd", "center_difference_bwd"; the metrics entries: "region_stats_fwd",
- * "region_stats_finish", "region_stats_bwd", "line_widths"; ...).
+ * "region_stats_finish", "region_stats_bwd", "line_widths"; the tolerance entries: "tolerance_fwd",
+ * "tolerance_heights", "tolerance_bwd"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

@@ -33,7 +33,8 @@ def install_reference_aliases():
             importlib.import_module(f"{__name__}.{sub}")
         except ModuleNotFoundError:
             pass
-    sys.modules["ifta"] = importlib.import_module(f"{__name__}.ifta")  # a module of this port alone
+    for own in ("ifta", "tolerance"):  # modules of this port alone
+        sys.modules[own] = importlib.import_module(f"{__name__}.{own}")
     for name in _ALIASES:
         mod = importlib.import_module(f"{__name__}.{name}")
         sys.modules[name] = mod

@@ -57,6 +57,7 @@ EXPORTED = [
     "thz_ifta_target_stats_workspace_size", "thz_ifta_target_stats", "thz_ifta_target_project", "thz_ifta_doe_project",
     "thz_fdtd_workspace_size", "thz_fdtd_setup", "thz_fdtd_run", "thz_fdtd_monitors", "thz_fdtd_fields",
     "thz_fdtd_material",
+    "thz_tolerance_modulate_forward", "thz_tolerance_modulate_backward",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -327,6 +328,21 @@ class FdtdDesc(ctypes.Structure):
                 ("cacb", ctypes.c_void_p)]        # const float* host [10]
 
 
+TOL_TAG_SCALE, TOL_TAG_LEVEL, TOL_TAG_ROUGH = 0x5343414C, 0x4C45564C, 0x524F5547  # "SCAL", "LEVL", "ROUG"
+TOL_ROUGH_NONE, TOL_ROUGH_UNIFORM, TOL_ROUGH_NORMAL = 0, 1, 2
+
+
+class ToleranceDesc(ctypes.Structure):
+    _fields_ = [("K", ctypes.c_int), ("first", ctypes.c_longlong), ("Bf", ctypes.c_int),
+                ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("hs", ctypes.c_int), ("ws", ctypes.c_int),
+                ("L", ctypes.c_int), ("sigma_level", ctypes.c_float * THZ_MAX_LUT),
+                ("sigma_scale", ctypes.c_float), ("rough_kind", ctypes.c_int), ("rough", ctypes.c_float),
+                ("lo", ctypes.c_float), ("hi", ctypes.c_float),
+                ("epsilon", ctypes.c_float), ("tand", ctypes.c_float),
+                ("wavelengths", ctypes.POINTER(ctypes.c_float)),  # host [C]
+                ("rng", ctypes.c_void_p), ("stream", ctypes.c_uint)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -447,6 +463,10 @@ def _declare(lib):
     lib.thz_fdtd_monitors.argtypes = [fd, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.thz_fdtd_fields.argtypes = [fd, c_void_p, c_size_t, c_void_p, c_void_p]
     lib.thz_fdtd_material.argtypes = [fd, c_void_p, c_size_t, c_void_p, c_void_p]
+    td = ctypes.POINTER(ToleranceDesc)
+    lib.thz_tolerance_modulate_forward.argtypes = [td, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.thz_tolerance_modulate_backward.argtypes = [td, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_size_t, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,

@@ -1,7 +1,8 @@
 // Device helpers shared by the propagator kernels (ASM, CZT, RSC) and the DOE kernels: the T / U
 // layouts, sincos and the RS kernel, apertures, the DOE transmission, the counter-based generator
-// (rng_bits, rng_u01, rng_exp1) and the MSE loss sink.  The streaming lane, the fixed-order reduction
-// and the partial sums of the add-on units live in thz_stream.hpp, the noise samplers in thz_noise.hip.
+// (rng_bits, rng_u01, rng_exp1, rng_normal) and the MSE loss sink.  The streaming lane, the fixed-order
+// reduction and the partial sums of the add-on units live in thz_stream.hpp, the other noise samplers in
+// thz_noise.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -349,6 +350,22 @@ __device__ __forceinline__ float rng_u01(const unsigned* rng, unsigned stream, u
 __device__ __forceinline__ float rng_exp1(const unsigned* rng, unsigned stream, unsigned idx) {
   const float e = -logf((float)((unsigned)(rng_bits(rng, stream, idx) >> 40) + 1u) * (1.0f / 16777216.0f));
   return fmaxf(e, 5.96046448e-8f);
+}
+// Two independent standard normals from one rng_bits word (torch.randn): Box-Muller on two 24-bit
+// uniforms, r = sqrt(-2 log u1) with u1 = (b1 + 1) / 2^24 in (0, 1] as in rng_exp1 (log(0) cannot
+// occur), angle u2 = b2 / 2^24 in [0, 1) revolutions -- the unit of v_sin_f32 / v_cos_f32 -- giving
+// (r cos, r sin).  The smallest u1 bounds |n| by sqrt(2 * 24 * ln 2) = 5.768 (the normal mass beyond
+// it is 8e-9).  A real draw takes .x; a complex draw takes both.  Shared by the noise samplers
+// (thz_noise.hip) and the fabrication-tolerance screen (thz_tolerance.hip).
+__device__ __forceinline__ float2 rng_normal2(const unsigned* rng, unsigned stream, unsigned idx) {
+  const unsigned long long w = rng_bits(rng, stream, idx);
+  const float u1 = (float)((unsigned)(w >> 40) + 1u) * (1.0f / 16777216.0f);
+  const float u2 = (float)((unsigned)(w >> 16) & 0xFFFFFFu) * (1.0f / 16777216.0f);
+  const float r = sqrtf(-2.0f * logf(u1));
+  return make_float2(r * __builtin_amdgcn_cosf(u2), r * __builtin_amdgcn_sinf(u2));
+}
+__device__ __forceinline__ float rng_normal(const unsigned* rng, unsigned stream, unsigned idx) {
+  return rng_normal2(rng, stream, idx).x;
 }
 
 // noisy height at a source pixel: h + (u - 0.5) * 2 * tol  (:85); u == nullptr: the device

@@ -33,21 +33,8 @@ namespace thz {
 // forward and its backward regenerate the same draw and a result never depends on the launch geometry
 // or on what a neighbouring lane does.  fp32, contraction off.
 // ---------------------------------------------------------------------------------------------
-// Two independent standard normals from one rng_bits word (torch.randn): Box-Muller on two 24-bit
-// uniforms, r = sqrt(-2 log u1) with u1 = (b1 + 1) / 2^24 in (0, 1] as in rng_exp1 (log(0) cannot
-// occur), angle u2 = b2 / 2^24 in [0, 1) revolutions -- the unit of v_sin_f32 / v_cos_f32 -- giving
-// (r cos, r sin).  The smallest u1 bounds |n| by sqrt(2 * 24 * ln 2) = 5.768 (the normal mass beyond
-// it is 8e-9).  A real draw takes .x; a complex draw takes both.
-__device__ __forceinline__ float2 rng_normal2(const unsigned* rng, unsigned stream, unsigned idx) {
-  const unsigned long long w = rng_bits(rng, stream, idx);
-  const float u1 = (float)((unsigned)(w >> 40) + 1u) * (1.0f / 16777216.0f);
-  const float u2 = (float)((unsigned)(w >> 16) & 0xFFFFFFu) * (1.0f / 16777216.0f);
-  const float r = sqrtf(-2.0f * logf(u1));
-  return make_float2(r * __builtin_amdgcn_cosf(u2), r * __builtin_amdgcn_sinf(u2));
-}
-__device__ __forceinline__ float rng_normal(const unsigned* rng, unsigned stream, unsigned idx) {
-  return rng_normal2(rng, stream, idx).x;
-}
+// The standard normals rng_normal2 / rng_normal (Box-Muller on two 24-bit uniforms of one rng_bits
+// word, |n| <= 5.768) live next to rng_bits in thz_dev.hpp.
 // complex standard normal, variance 1 in total (torch.randn of a complex dtype: 1/2 per component)
 __device__ __forceinline__ float2 rng_cnormal(const unsigned* rng, unsigned stream, unsigned idx) {
   const float2 z = rng_normal2(rng, stream, idx);
