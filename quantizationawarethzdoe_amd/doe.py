@@ -13,11 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .propagation import _require_device, _stream_handle
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+from ._call import _require_device, call
 
 
 def _doe_desc(B, C, H, W, hs, ws, tol, eps, tand, wavelengths, rng=None):
@@ -44,9 +40,7 @@ class _Modulate(torch.autograd.Function):
         d = _doe_desc(B, C, H, W, hs, ws, tol, eps, tand, wavelengths, rng if noise is None else None)
         out = torch.empty_like(field)
         hfull = torch.empty((H, W), dtype=torch.float32, device=field.device)
-        with torch.cuda.device(field.device):
-            _lib.check(_lib.lib().thz_doe_modulate_forward(ctypes.byref(d), _ptr(field), _ptr(height), _ptr(noise),
-                                                           _ptr(out), _ptr(hfull), _stream_handle()))
+        call(_lib.lib().thz_doe_modulate_forward, d, field, height, noise, out, hfull, device=field.device)
         ctx.save_for_backward(field, height, noise)
         ctx.cfg = (tol, eps, tand, wavelengths, rng)
         ctx.mark_non_differentiable(hfull)
@@ -70,9 +64,7 @@ def modulate_backward(g, field, height, noise, tol, eps, tand, wavelengths, need
     g = g.contiguous()
     gf = torch.empty_like(field) if need_field else None
     gh = torch.empty((hs, ws), dtype=torch.float32, device=field.device) if need_height else None
-    with torch.cuda.device(field.device):
-        _lib.check(_lib.lib().thz_doe_modulate_backward(ctypes.byref(d), _ptr(g), _ptr(field), _ptr(height),
-                                                        _ptr(noise), _ptr(gf), _ptr(gh), _stream_handle()))
+    call(_lib.lib().thz_doe_modulate_backward, d, g, field, height, noise, gf, gh, device=field.device)
     return gf, gh
 
 
@@ -88,10 +80,8 @@ def modulate_quant_backward(g, field, height, noise, tol, eps, tand, wavelengths
     g = g.contiguous()
     gf = torch.empty_like(field) if need_field else None
     gw = grad_slot(link.param, link.w)
-    with torch.cuda.device(field.device):
-        _lib.check(_lib.lib().thz_doe_quant_backward(ctypes.byref(d), ctypes.byref(q), _ptr(g), _ptr(field),
-                                                     _ptr(height), _ptr(noise), _ptr(link.w), _ptr(link.ysoft),
-                                                     _ptr(gf), _ptr(gw), _stream_handle()))
+    call(_lib.lib().thz_doe_quant_backward, d, q, g, field, height, noise, link.w, link.ysoft, gf, gw,
+         device=field.device)
     return gf, gw.reshape(link.weight.shape)
 
 
@@ -213,9 +203,7 @@ class _Quantize(torch.autograd.Function):
             ysoft = torch.empty(expo_shape, dtype=torch.float32, device=w.device)
         else:
             ysoft = None
-        with torch.cuda.device(w.device):
-            _lib.check(_lib.lib().thz_quant_forward(ctypes.byref(d), _ptr(w), _ptr(expo), _ptr(out), _ptr(ysoft),
-                                                    _stream_handle()))
+        call(_lib.lib().thz_quant_forward, d, w, expo, out, ysoft, device=w.device)
         ctx.save_for_backward(w, ysoft)
         ctx.cfg = cfg
         if keep is not None:  # for the QuantLink
@@ -228,9 +216,7 @@ class _Quantize(torch.autograd.Function):
         kind, hq, wq, mirror, lut, kw = ctx.cfg
         d = _quant_desc(kind, hq, wq, mirror, lut, **kw)
         gw = torch.empty_like(w)
-        with torch.cuda.device(w.device):
-            _lib.check(_lib.lib().thz_quant_backward(ctypes.byref(d), _ptr(w), _ptr(ysoft), _ptr(g.contiguous()),
-                                                     _ptr(gw), _stream_handle()))
+        call(_lib.lib().thz_quant_backward, d, w, ysoft, g.contiguous(), gw, device=w.device)
         return gw, None, None, None, None
 
 
@@ -267,8 +253,7 @@ class _Radial(torch.autograd.Function):
     def forward(ctx, prof, R, H, W):
         p = prof.detach().contiguous().float().reshape(-1)
         out = torch.empty((H, W), dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().thz_radial_forward(_ptr(p), R, H, W, _ptr(out), _stream_handle()))
+        call(_lib.lib().thz_radial_forward, p, R, H, W, out, device=p.device)
         ctx.cfg = (prof.shape, R, H, W)
         return out
 
@@ -276,8 +261,7 @@ class _Radial(torch.autograd.Function):
     def backward(ctx, g):
         shape, R, H, W = ctx.cfg
         gp = torch.empty(R, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            _lib.check(_lib.lib().thz_radial_backward(_ptr(g.contiguous()), R, H, W, _ptr(gp), _stream_handle()))
+        call(_lib.lib().thz_radial_backward, g.contiguous(), R, H, W, gp, device=g.device)
         return gp.reshape(shape), None, None, None
 
 
@@ -290,8 +274,7 @@ class _RadialQuant(torch.autograd.Function):
     def forward(ctx, weight, prof, link, R, H, W):
         p = prof.detach().contiguous().float().reshape(-1)
         out = torch.empty((H, W), dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().thz_radial_forward(_ptr(p), R, H, W, _ptr(out), _stream_handle()))
+        call(_lib.lib().thz_radial_forward, p, R, H, W, out, device=p.device)
         ctx.link, ctx.cfg = link, (R, H, W)
         return out
 
@@ -302,10 +285,8 @@ class _RadialQuant(torch.autograd.Function):
         (kind, hq, wq, mirror, lut), kw = link.desc_args()
         d = _quant_desc(kind, hq, wq, mirror, lut, **kw)
         gw = grad_slot(link.param, link.w)
-        with torch.cuda.device(g.device):
-            _lib.check(_lib.lib().thz_radial_quant_backward(ctypes.byref(d), _ptr(g.contiguous()), R, H, W,
-                                                            _ptr(link.w), _ptr(link.ysoft), _ptr(gw),
-                                                            _stream_handle()))
+        call(_lib.lib().thz_radial_quant_backward, d, g.contiguous(), R, H, W, link.w, link.ysoft, gw,
+             device=g.device)
         return gw.reshape(link.weight.shape), None, None, None, None, None
 
 

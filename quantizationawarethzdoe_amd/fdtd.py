@@ -50,14 +50,13 @@ field is that of the conjugate element (a lens diverges)::
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from .propagation import _require_device, _stream_handle
+from ._call import _require_device, call, workspace
 
 CPML_ORDER = 3
 CPML_SIGMA = 0.8     # sigma_max = CPML_SIGMA (CPML_ORDER + 1) / (eta0 Delta)
@@ -111,10 +110,6 @@ def step_table(n_steps, courant, cpw, ramp_periods, settle_steps, acc_steps):
     return np.ascontiguousarray(np.stack([f32(c * ramp), f32(s * ramp), dc, ds, flag], axis=1))
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
 class FDTDResult:
     """``planes`` [n, 3, Ny, Nx], ``zx`` [3, Nz, Nx], ``zy`` [3, Nz, Ny] complex64 phasors of (Ex, Ey, Ez) (None
     where not asked for); ``z`` [Nz] float64, metres above the top of the base plate; ``plane_z`` the planes'
@@ -158,22 +153,17 @@ class FDTDState:
         self.cpml = cpml_tables(sim.npml, sim.courant)
         self.cacb = cacb_table(sim.eps, sim.tand, sim.courant, sim.cpw)
         d = self.desc = sim._desc(plan, self.tab, self.cpml, self.cacb)
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(_lib.lib().thz_fdtd_workspace_size(ctypes.byref(d), ctypes.byref(nbytes)))
-        self.ws = torch.empty(nbytes.value, dtype=torch.uint8, device=sim.device)
+        self.ws = workspace(_lib.lib().thz_fdtd_workspace_size, d, device=sim.device)
         self.enqueued = 0
-        with torch.cuda.device(sim.device):
-            _lib.check(_lib.lib().thz_fdtd_setup(ctypes.byref(d), _p(sim.height), _p(incident), _p(self.ws),
-                                                 self.ws.numel(), _stream_handle()))
-            torch.cuda.current_stream().synchronize()  # the tables are host arrays of this object: copied by now
+        call(_lib.lib().thz_fdtd_setup, d, sim.height, incident, self.ws, self.ws.numel(), device=sim.device)
+        # the tables are host arrays of this object: copied by now
+        torch.cuda.current_stream(sim.device).synchronize()
 
     def advance(self, n):
         n = int(n)
         if n < 0 or self.enqueued + n > self.plan["n_table"]:
             raise ValueError(f"FDTD: {self.enqueued} + {n} steps for a step table of {self.plan['n_table']}")
-        with torch.cuda.device(self.sim.device):
-            _lib.check(_lib.lib().thz_fdtd_run(ctypes.byref(self.desc), _p(self.ws), self.ws.numel(), n,
-                                               _stream_handle()))
+        call(_lib.lib().thz_fdtd_run, self.desc, self.ws, self.ws.numel(), n, device=self.sim.device)
         self.enqueued += n   # a captured call counts once: the steps of its first replay
         return self
 
@@ -181,18 +171,14 @@ class FDTDState:
         """[6, Nz, Ny, Nx] float32: Ex, Ey, Ez, Hx, Hy, Hz (H times eta0) as they stand."""
         s = self.sim
         out = torch.empty((6, s.Nz, s.Ny, s.Nx), dtype=torch.float32, device=s.device)
-        with torch.cuda.device(s.device):
-            _lib.check(_lib.lib().thz_fdtd_fields(ctypes.byref(self.desc), _p(self.ws), self.ws.numel(), _p(out),
-                                                  _stream_handle()))
+        call(_lib.lib().thz_fdtd_fields, self.desc, self.ws, self.ws.numel(), out, device=s.device)
         return out
 
     def material(self):
         """[Nz, Ny, Nx] int32: the rasterised word nx | ny << 3 | nz << 6 of edge counts."""
         s = self.sim
         out = torch.empty((s.Nz, s.Ny, s.Nx), dtype=torch.int16, device=s.device)
-        with torch.cuda.device(s.device):
-            _lib.check(_lib.lib().thz_fdtd_material(ctypes.byref(self.desc), _p(self.ws), self.ws.numel(), _p(out),
-                                                    _stream_handle()))
+        call(_lib.lib().thz_fdtd_material, self.desc, self.ws, self.ws.numel(), out, device=s.device)
         return out.to(torch.int32) & 0xffff
 
     def monitors(self):
@@ -202,9 +188,7 @@ class FDTDState:
         planes = torch.empty((len(p["planes"]), 3, s.Ny, s.Nx), dtype=c64, device=dev) if p["planes"] else None
         zx = torch.empty((3, s.Nz, s.Nx), dtype=c64, device=dev) if p["row"] is not None else None
         zy = torch.empty((3, s.Nz, s.Ny), dtype=c64, device=dev) if p["col"] is not None else None
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().thz_fdtd_monitors(ctypes.byref(self.desc), _p(self.ws), self.ws.numel(), _p(planes),
-                                                    _p(zx), _p(zy), _stream_handle()))
+        call(_lib.lib().thz_fdtd_monitors, self.desc, self.ws, self.ws.numel(), planes, zx, zy, device=dev)
         return planes, zx, zy
 
 

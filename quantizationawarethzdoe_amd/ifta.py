@@ -90,7 +90,7 @@ class IFTA:
         self.spacing = spacing
         self.kappa = _doe.phase_scale(self.wavelength, self.eps)
         self.h_max = 2.0 * torch.pi / self.kappa
-        self.lut = optics._table(lut, "IFTA", torch.float32)
+        self.lut = optics.heightmap.host_table(lut, "IFTA", torch.float32)
         if not 1 <= len(self.lut) <= _lib.THZ_MAX_LUT:
             raise ValueError(f"IFTA: {len(self.lut)} levels; the kernels take 1 .. {_lib.THZ_MAX_LUT} (THZ_MAX_LUT)")
         self.doe_shape = (int(doe_shape[0]), int(doe_shape[1]))

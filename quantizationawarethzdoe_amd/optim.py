@@ -16,12 +16,10 @@ Plain fp32 CUDA parameters only (no amsgrad, maximize, or sparse gradients): any
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
-from .propagation import _stream_handle
+from ._call import call
 
 
 class _ThzAdamBase(torch.optim.Optimizer):
@@ -91,8 +89,7 @@ class _ThzAdamBase(torch.optim.Optimizer):
         d = _lib.AdamDesc(lr=float(group["lr"]), beta1=float(b1), beta2=float(b2), eps=float(group["eps"]),
                           weight_decay=float(group["weight_decay"]), decoupled=int(self._decoupled),
                           nparams=len(ps), done=done.data_ptr())
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().thz_adam_step(ctypes.byref(d), arr, _stream_handle()))
+        call(_lib.lib().thz_adam_step, d, arr, device=dev)
 
 
 class Adam(_ThzAdamBase):

@@ -17,12 +17,7 @@ import typing
 import torch
 
 from . import _lib
-
-
-def _require_device(t: torch.Tensor, what: str):
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: the MI355X path needs a ROCm device tensor (got device {t.device}); "
-                           "this framework has no CPU compute path")
+from ._call import _launch, _require_device, call, loss_stats
 
 
 def kernel_dtype(data: torch.Tensor, who: str, wavelengths=None) -> torch.Tensor:
@@ -38,24 +33,6 @@ def kernel_dtype(data: torch.Tensor, who: str, wavelengths=None) -> torch.Tensor
         raise TypeError(f"{who}: the MI355X kernels compute in complex64 or complex128; got {data.dtype}")
     want = torch.complex128 if fp64 else torch.complex64
     return data if data.dtype == want else data.to(want)
-
-
-def _stream_handle():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _launch(size_fn, run_fn, d, device, *args):
-    """One call of a workspace-taking entry point on ``device``'s current stream:
-    run_fn(&d, *args, workspace, bytes, stream) with the workspace size_fn(&d) asks for.  Tensors
-    among ``args`` pass as their data pointers, None as NULL, anything else (a row, a byref'd
-    descriptor) as it is."""
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(size_fn(ctypes.byref(d), ctypes.byref(nbytes)))
-    ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=device)
-    args = [ctypes.c_void_p(a.data_ptr()) if torch.is_tensor(a) else a for a in args]
-    with torch.cuda.device(device):
-        _lib.check(run_fn(ctypes.byref(d), *args, ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
-                          _stream_handle()))
 
 
 def _bandlimit(b):
@@ -221,9 +198,7 @@ def asm_transfer_function(wavelengths, spacing, z, H, W, pad_h, pad_w, bandlimit
     d = _asm_desc(1, len(wavelengths), int(H), int(W), int(pad_h), int(pad_w), True, bl, wavelengths, spacing,
                   [float(z)], False)
     out = torch.empty((1, len(wavelengths), H + 2 * pad_h, W + 2 * pad_w), dtype=torch.complex64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().thz_asm_transfer_function(ctypes.byref(d), ctypes.c_void_p(out.data_ptr()),
-                                                         _stream_handle()))
+    call(_lib.lib().thz_asm_transfer_function, d, out, device=dev)
     return out
 
 
@@ -238,10 +213,8 @@ def rs_kernel(meshx, meshy, z, wavelengths):
     wl = [float(v) for v in wavelengths]
     arr = _lib.float_array(wl)
     out = torch.empty((1, len(wl)) + shape, dtype=torch.complex64, device=mx.device)
-    with torch.cuda.device(mx.device):
-        _lib.check(_lib.lib().thz_rs_kernel(ctypes.c_void_p(mx.data_ptr()), ctypes.c_void_p(my.data_ptr()),
-                                            int(mx.numel()), ctypes.c_float(float(z)), ctypes.cast(arr, ctypes.c_void_p), len(wl),
-                                            ctypes.c_void_p(out.data_ptr()), _stream_handle()))
+    call(_lib.lib().thz_rs_kernel, mx, my, int(mx.numel()), ctypes.c_float(float(z)), ctypes.cast(arr, ctypes.c_void_p),
+         len(wl), out, device=mx.device)
     return out
 
 
@@ -276,8 +249,8 @@ class _AsmModulatedFunction(torch.autograd.Function):
         L = _lib.lib()
         out = torch.empty((len(zs), B, C, Ho, Wo), dtype=torch.complex64, device=field.device)
         hfull = torch.empty((H, W), dtype=torch.float32, device=field.device)
-        _launch(L.thz_asm_workspace_size, L.thz_asm_forward_modulated, d, field.device, ctypes.byref(m), field, h,
-                pend.noise, hfull, out)
+        _launch(L.thz_asm_workspace_size, L.thz_asm_forward_modulated, d, field.device, m, field, h, pend.noise, hfull,
+                out)
         if pend.hfull is None:
             pend.hfull = hfull
         ctx.save_for_backward(field, h)
@@ -361,8 +334,7 @@ class _AsmLossFunction(torch.autograd.Function):
         dev = field.device
         out = torch.empty((Z, B, C, Ho, Wo), dtype=torch.complex64, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        stats = torch.empty(L.thz_intensity_mse_workspace_size(ctypes.byref(ld)) // 4, dtype=torch.float32,
-                            device=dev)
+        stats = loss_stats(ld, dev)
         h = hfull = noise = None
         m = None
         if pend is not None:
@@ -370,8 +342,8 @@ class _AsmLossFunction(torch.autograd.Function):
             hfull = torch.empty((H, W), dtype=torch.float32, device=dev)
             noise = pend.noise
             m = pend.desc()
-        _launch(L.thz_asm_workspace_size, L.thz_asm_forward_loss, d, dev, ctypes.byref(m) if m is not None else None,
-                field, h, noise, hfull, ctypes.byref(ld), t4, out, loss, stats)
+        _launch(L.thz_asm_workspace_size, L.thz_asm_forward_loss, d, dev, m, field, h, noise, hfull, ld, t4, out, loss,
+                stats)
         if pend is not None and pend.hfull is None:
             pend.hfull = hfull
         ctx.save_for_backward(field, h, out, t4, stats)
@@ -399,8 +371,7 @@ class _AsmLossFunction(torch.autograd.Function):
             gm = torch.empty((B, C, H, W), dtype=torch.complex64, device=out.device)
             g = g_loss.detach().float().contiguous()
             go = g_out.contiguous() if g_out is not None else None
-            _launch(L.thz_asm_workspace_size, L.thz_asm_adjoint_loss, d, out.device, ctypes.byref(ld), out, t4, stats,
-                    g, go, gm)
+            _launch(L.thz_asm_workspace_size, L.thz_asm_adjoint_loss, d, out.device, ld, out, t4, stats, g, go, gm)
         gh = gw = None
         pend = ctx.pend
         if pend is None:
@@ -462,9 +433,7 @@ def fft_rows(x, inverse=False):
     n = x.shape[-1]
     rows = x.numel() // n
     fn = _lib.lib().thz_fft64_rows if x.dtype == torch.complex128 else _lib.lib().thz_fft_rows
-    with torch.cuda.device(x.device):
-        _lib.check(fn(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), rows, n, int(inverse),
-                      _stream_handle()))
+    call(fn, x, out, rows, n, int(inverse), device=x.device)
     return out
 
 

@@ -351,10 +351,9 @@ class StepState:
 
     def fetch(self):
         """Captured as a step graph's first node: state <- ring[counter % depth], counter += 1."""
-        from quantizationawarethzdoe_amd import _lib
-        _lib.check(_lib.lib().thz_step_fetch(self._ring.data_ptr(), len(self._ring), self.width,
-                                             self.state.data_ptr(), self.counter.data_ptr(),
-                                             _prop._stream_handle()))
+        from quantizationawarethzdoe_amd import _call, _lib
+        _call.call(_lib.lib().thz_step_fetch, self._ring, len(self._ring), self.width, self.state, self.counter,
+                   device=self.state.device)
 
     @contextlib.contextmanager
     def installed(self, layers):

@@ -202,7 +202,7 @@ class ToleranceAnalysis:
         if K < 1 or chunk < 1:
             raise ValueError(f"ToleranceAnalysis.run: K = {K} and chunk = {chunk} must be >= 1")
         data = self.field.data
-        rng = optics._noise_state(data, rng)
+        rng = optics.noise.noise_state(data, rng)
         power = torch.empty((K, len(self.regions) + 1), dtype=torch.float64, device=data.device)  # all a run keeps
         with torch.no_grad():
             for first in range(0, K, chunk):

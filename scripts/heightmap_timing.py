@@ -4,7 +4,7 @@ a [8, 1, 2048, 2048] float32 map, and writes profiles/heightmap_timing.txt.
 
 Each call is bracketed by HIP events: 5 warm-ups, then the median of 20 runs, fused and torch
 alternated.  The torch forms are the op sequences the float64 path of the same functions runs
-(optics._lut_forward_torch / _lut_slope_torch / _center_difference_torch), here in float32.  The
+(optics.heightmap.lut_forward_torch / lut_slope_torch / center_difference_torch), here in float32.  The
 argmin snap runs with the notebooks' 10-level table on both sides; the bucketize forms with its nine
 midpoints and the reference's modulo.  Every call takes the next of three input maps (403 MB in all,
 more than the 256 MB last-level cache), so no call finds its input resident from the call before;
@@ -33,7 +33,7 @@ SHAPE = (8, 1, 2048, 2048)
 HBM_PEAK = 8.0e12
 WARMUP, RUNS = 5, 20
 LUT = tuple(torch.tensor([float(v) for v in (torch.arange(0, 10) * (1e-3 / 10))], dtype=torch.float32).tolist())
-MID = optics._lut_mid(LUT, torch.float32)
+MID = optics.heightmap.lut_mid(LUT, torch.float32)
 S = 2.5
 # bytes per element of each kernel
 MODEL = {"lut_quantize_fwd": 12, "lut_quantize_bwd": 16, "tv_fwd": 4, "center_difference": 12, "tv_bwd": 8,
@@ -62,15 +62,15 @@ def peak_bytes(fn):
 def torch_quantize(x, mode, kind):
     """The reference's sequence as one autograd function would run it: forward, then grad_out * slope."""
     wrap = mode == _lib.LUTQ_BUCKETIZE
-    q, idx = optics._lut_forward_torch(x, LUT, MID, mode, wrap)
+    q, idx = optics.heightmap.lut_forward_torch(x, LUT, MID, mode, wrap)
     if kind is None:
         return q
     g = torch.ones_like(x)
-    return g if kind == _lib.LUTQ_GRAD_IDENTITY else g * optics._lut_slope_torch(x, idx, LUT, kind, S)
+    return g if kind == _lib.LUTQ_GRAD_IDENTITY else g * optics.heightmap.lut_slope_torch(x, idx, LUT, kind, S)
 
 
 def torch_tv(x):
-    dx, dy = optics._center_difference_torch(x.reshape(-1, *x.shape[-2:]))
+    dx, dy = optics.heightmap.center_difference_torch(x.reshape(-1, *x.shape[-2:]))
     return dx.abs().mean() + dy.abs().mean()
 
 
@@ -133,7 +133,7 @@ def cases(nxt, nxt_off, up):
         ("nns_sigmoid forward + backward, s = 2.5", fused_q("bucketize", "sigmoid"),
          torch_q(_lib.LUTQ_BUCKETIZE, _lib.LUTQ_GRAD_SIGMOID)),
         ("center_difference (forward)", nograd(optics.center_difference),
-         nograd(lambda t: optics._center_difference_torch(t.reshape(-1, *t.shape[-2:])))),
+         nograd(lambda t: optics.heightmap.center_difference_torch(t.reshape(-1, *t.shape[-2:])))),
         ("total_variation (forward)", nograd(optics.total_variation), nograd(torch_tv)),
         ("total_variation forward + backward", fused_tv_fb, torch_tv_fb),
     ]

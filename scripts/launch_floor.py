@@ -16,7 +16,7 @@ import ctypes  # noqa: E402
 
 import torch  # noqa: E402
 
-from quantizationawarethzdoe_amd import _lib, propagation as P  # noqa: E402
+from quantizationawarethzdoe_amd import _call, _lib, propagation as P  # noqa: E402
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 R = int(sys.argv[2]) if len(sys.argv) > 2 else 50
@@ -35,7 +35,7 @@ def aten():
 
 
 def radial():
-    s = P._stream_handle()
+    s = _call._stream_handle()
     for _ in range(N):
         _lib.check(L.thz_radial_forward(ctypes.c_void_p(prof.data_ptr()), 8, 4, 4, ctypes.c_void_p(hmap.data_ptr()), s))
 

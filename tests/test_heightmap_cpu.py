@@ -145,12 +145,12 @@ def test_argument_errors_and_cpu_tensors():
     # the descriptor checks run on the host
     import ctypes
     L = ctypes.c_void_p(8)
-    d = optics._lut_desc(4, _lib.LUTQ_BUCKETIZE, False, 0, [0.0] * 17, ())
+    d = optics.heightmap.lut_desc(4, _lib.LUTQ_BUCKETIZE, False, 0, [0.0] * 17, ())
     assert _lib.lib().thz_lut_quantize_forward(ctypes.byref(d), L, L, L, None) == _lib.THZ_E_UNSUPPORTED
-    d = optics._lut_desc(4, _lib.LUTQ_BUCKETIZE, True, 0, [0.0, 1.0], ())
+    d = optics.heightmap.lut_desc(4, _lib.LUTQ_BUCKETIZE, True, 0, [0.0, 1.0], ())
     assert _lib.lib().thz_lut_quantize_forward(ctypes.byref(d), L, L, L, None) == _lib.THZ_E_ARG
     assert b"thresholds" in _lib.lib().thz_last_error()
-    d = optics._lut_desc(4, 0, False, 7, [0.0, 1.0], ())
+    d = optics.heightmap.lut_desc(4, 0, False, 7, [0.0, 1.0], ())
     assert _lib.lib().thz_lut_quantize_backward(ctypes.byref(d), L, L, L, L, L, None) == _lib.THZ_E_ARG
     n = ctypes.c_size_t(0)
     assert _lib.lib().thz_tv_workspace_size(0, 4, 4, ctypes.byref(n)) == _lib.THZ_E_ARG

@@ -124,7 +124,7 @@ def _check_forward(x, lut, mode, wrap, thr, offset=0):
     if mode == "bucketize":
         kw["midvals"] = thr
     q, idx = optics.lut_quantize(xd, lut, **kw)
-    tq, tidx = optics._lut_forward_torch(xd, tuple(lut), tuple(thr), optics._LUT_MODES[mode], wrap)
+    tq, tidx = optics.heightmap.lut_forward_torch(xd, tuple(lut), tuple(thr), optics.heightmap.LUT_MODES[mode], wrap)
     assert idx.dtype == torch.int64 and not q.requires_grad and q.shape == x.shape
     assert torch.equal(idx, tidx), (mode, wrap, len(lut), x.numel())
     assert _bits(q, tq)
@@ -156,7 +156,7 @@ def test_quantize_forward_nan_and_wrap_rules():
     lut = TABLES["u4"]
     thr = _mid32(lut)
     x = torch.tensor([float("nan"), lut[-1] + 1.0, thr[-1], lut[0] - 1.0, 0.0, -0.0]).to(_dev())
-    assert optics._lut_forward_torch(x, tuple(lut), tuple(thr), _lib.LUTQ_BUCKETIZE, False)[1].tolist() == [3, 3, 3, 0, 0, 0]
+    assert optics.heightmap.lut_forward_torch(x, tuple(lut), tuple(thr), _lib.LUTQ_BUCKETIZE, False)[1].tolist() == [3, 3, 3, 0, 0, 0]
     _, idx = optics.lut_quantize(x, lut, surrogate=None)
     assert idx.tolist() == [3, 3, 3, 0, 0, 0]  # a NaN counts every threshold, as torch.bucketize
     _, idx = optics.lut_quantize(x, lut, wrap=True, surrogate=None)
@@ -293,7 +293,7 @@ def test_quantize_backward_float64_runs_the_torch_sequence():
 def test_identity_kind_of_the_c_entry():
     g = torch.randn(1027, device=_dev())
     out = torch.empty_like(g)
-    d = optics._lut_desc(g.numel(), 0, False, _lib.LUTQ_GRAD_IDENTITY, (0.0, 1.0), ())
+    d = optics.heightmap.lut_desc(g.numel(), 0, False, _lib.LUTQ_GRAD_IDENTITY, (0.0, 1.0), ())
     _lib.check(_lib.lib().thz_lut_quantize_backward(ctypes.byref(d), None, None, ctypes.c_void_p(g.data_ptr()), None,
                                                     ctypes.c_void_p(out.data_ptr()),
                                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))

@@ -198,8 +198,8 @@ def test_python_argument_errors_before_any_launch():
     with pytest.raises(ValueError, match="beta"):
         optics.ifta_target_project(U, torch.zeros(8, 8), torch.zeros(2, dtype=torch.float64), beta=2.0)
     with pytest.raises(ValueError, match="whole number"):
-        optics._ifta_doe_desc(1, 8, 8, (3, 4), LAM, EPS, (0.0,), 0)
+        optics.ifta.ifta_doe_desc(1, 8, 8, (3, 4), LAM, EPS, (0.0,), 0)
     with pytest.raises(ValueError, match="17 levels"):
-        optics._ifta_doe_desc(1, 8, 8, (4, 4), LAM, EPS, tuple(1e-5 * i for i in range(17)), 0)
-    d = optics._ifta_doe_desc(2, 8, 6, (4, 3), LAM, EPS, (0.0, 1e-4), 2)
+        optics.ifta.ifta_doe_desc(1, 8, 8, (4, 4), LAM, EPS, tuple(1e-5 * i for i in range(17)), 0)
+    d = optics.ifta.ifta_doe_desc(2, 8, 6, (4, 3), LAM, EPS, (0.0, 1e-4), 2)
     assert (d.hs, d.ws, d.L, d.incident_planes) == (4, 3, 2, 2) and d.lut[1] == pytest.approx(1e-4)

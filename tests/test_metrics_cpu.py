@@ -150,18 +150,18 @@ def test_python_argument_errors_before_any_launch():
     from quantizationawarethzdoe_amd import optics
     dev = torch.device("cpu")
     with pytest.raises(ValueError, match="17 regions"):
-        optics._region_table([[1, 1, 1]] * 17, "circ", "region_stats", dev)
+        optics.metrics.region_table([[1, 1, 1]] * 17, "circ", "region_stats", dev)
     with pytest.raises(ValueError, match=r"\[K, 3\]"):
-        optics._region_table([[1, 1]], "circ", "region_stats", dev)
+        optics.metrics.region_table([[1, 1]], "circ", "region_stats", dev)
     with pytest.raises(ValueError, match="kind"):
-        optics._region_table([[1, 1, 1]], "disc", "region_stats", dev)
+        optics.metrics.region_table([[1, 1, 1]], "disc", "region_stats", dev)
     with pytest.raises(ValueError, match="rectangle"):
-        optics._region_table([[1, 1, 1]], "rect", "region_stats", dev)
+        optics.metrics.region_table([[1, 1, 1]], "rect", "region_stats", dev)
     with pytest.raises(ValueError, match="finite"):
-        optics._region_table([[1, 1, -1]], "circ", "region_stats", dev)
-    K, host, devtab = optics._region_table([[1, 2, 3, 4], [5, 6, 7, 8]], ["circ", "rect"], "region_stats", dev)
+        optics.metrics.region_table([[1, 1, -1]], "circ", "region_stats", dev)
+    K, host, devtab = optics.metrics.region_table([[1, 2, 3, 4], [5, 6, 7, 8]], ["circ", "rect"], "region_stats", dev)
     assert K == 2 and devtab is None and (host[1].kind, host[1].cr, host[1].b) == (1, 5.0, 8.0)
-    assert optics._region_table([], "circ", "region_stats", dev)[0] == 0
+    assert optics.metrics.region_table([], "circ", "region_stats", dev)[0] == 0
     with pytest.raises(RuntimeError, match="ROCm device"):
         optics.region_stats(torch.zeros(4, 4), [[1, 1, 1]])
     with pytest.raises(RuntimeError, match="ROCm device"):

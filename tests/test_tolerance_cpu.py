@@ -93,8 +93,8 @@ def test_fabrication_model_validation():
     with pytest.raises(ValueError):
         F(sigma_level=[1e-6, 1e-6]).for_levels(4)
     # what optics hands the kernel: a scalar level sigma serves every index, none means an empty table
-    assert optics._tolerance_cfg(F(sigma_level=2e-6), "t")[1] == (2e-6,) * 16
-    assert optics._tolerance_cfg(F(), "t") == (0.0, (), _lib.TOL_ROUGH_NONE, 0.0, 0.0, math.inf)
+    assert optics.tolerance.tolerance_cfg(F(sigma_level=2e-6), "t")[1] == (2e-6,) * 16
+    assert optics.tolerance.tolerance_cfg(F(), "t") == (0.0, (), _lib.TOL_ROUGH_NONE, 0.0, 0.0, math.inf)
 
 
 def test_tolerance_modulate_argument_errors():
