@@ -633,8 +633,9 @@ static void czt_layout(const thz_czt_desc* d, CztArgs* a, size_t* total) {
   // x_out = linspace(-outH dxo/2, outH dxo/2, outH), y_out likewise (Props/CZT_Prop.py:101-102)
   const double xo = (double)(float)((float)d->outH * d->odx / 2.0f);
   const double yo = (double)(float)((float)d->outW * d->ody / 2.0f);
-  make_pass(&a->pa, d->W, d->outH, -xo, xo, !d->adjoint);  // second reference Bluestein (:246): fx, outH
-  make_pass(&a->pb, d->H, d->outW, -yo, yo, !d->adjoint);  // first reference Bluestein (:243): fy, outW
+  // a one-point linspace is its start: x_out[-1] = x_out[0] = -xo, so M = 1 zooms onto f2 = f1
+  make_pass(&a->pa, d->W, d->outH, -xo, d->outH == 1 ? -xo : xo, !d->adjoint);  // second reference Bluestein (:246): fx, outH
+  make_pass(&a->pb, d->H, d->outW, -yo, d->outW == 1 ? -yo : yo, !d->adjoint);  // first reference Bluestein (:243): fy, outW
   a->ncbA = (d->outH + CB - 1) / CB;
   size_t off = 0;
   auto take = [&](size_t n) {
@@ -1123,8 +1124,8 @@ static void czt_slice_layout(const thz_czt_slice_desc* d, CztSliceArgs* a, size_
   a->ody = d->ody;
   const double xo = (double)(float)((float)d->outH * d->odx / 2.0f);
   const double yo = (double)(float)((float)d->outW * d->ody / 2.0f);
-  make_pass(&a->pa, d->W, d->outH, -xo, xo, false);
-  make_pass(&a->pb, d->H, d->outW, -yo, yo, false);
+  make_pass(&a->pa, d->W, d->outH, -xo, d->outH == 1 ? -xo : xo, false);  // one-point linspace: czt_layout
+  make_pass(&a->pb, d->H, d->outW, -yo, d->outW == 1 ? -yo : yo, false);
   const int nzc = std::min(d->Z, CZS_ZC);
   a->nz = nzc;
   // split H until the collapse grid has about CZS_WAVES waves, at least 16 rows per split
@@ -1222,8 +1223,10 @@ extern "C" int thz_czt_forward(const thz_czt_desc* d, const void* in, void* out,
   {
     KernelTimer kt("czt_rows", s);
     if (a.pa.nb) {
+      KernelTimer kb("czt_rows_blk", s);  // the overlap-add form also under a name of its own: which form a call took
       hipLaunchKernelGGL(d->W % CZB_BS ? czt_rows_blk<true> : czt_rows_blk<false>, dim3((a.BC * d->H + CZB_W - 1) / CZB_W), dim3(64 * CZB_W), czb_lds_bytes(CZB_W), s,
                          (const float2*)in, V, ws, a);
+      kb.stop();
     } else {
       on_pow2(a.pa.np2, [&](auto N) {
         hipLaunchKernelGGL(czt_rows<N()>, dim3(a.BC * d->H), dim3(thA), ldsA, s, (const float2*)in, V, ws, plA, a);
@@ -1237,8 +1240,10 @@ extern "C" int thz_czt_forward(const thz_czt_desc* d, const void* in, void* out,
     if (a.pb.nb) {
       // two half-block workgroups per V block; the grid rounded up to whole runs of 16 ids (sibling
       // halves b and b ^ 8), the ids past the last block exit at once
+      KernelTimer kb("czt_cols_blk", s);
       hipLaunchKernelGGL(d->H % CZB_BS ? czt_cols_blk<true> : czt_cols_blk<false>, dim3((a.BC * a.ncbA + 7) / 8 * 16), dim3(64 * CZB_WC), czb_cols_lds_bytes(),
                          s, (const float2*)V, (float2*)out, ws, a);
+      kb.stop();
     } else {
       on_pow2(a.pb.np2, [&](auto N) {
         hipLaunchKernelGGL(czt_cols<N()>, dim3(a.BC * d->outH), dim3(thB), ldsB, s, (const float2*)V, (float2*)out, ws, plB, a);

@@ -230,7 +230,8 @@ __device__ __forceinline__ void sincos_hw(float ang, float* sn, float* cs) {
 // Newton-refined reciprocal and sincos_hw: about 25 instructions instead of three IEEE divisions,
 // a square root and the polynomial sincos.  The phase k rho^2 / (r + |z|) (thousands of radians)
 // keeps ~1 ulp, the fp32 floor of its representation; the amplitude carries a few ulp.  Used by
-// the overlap-add CZT kernels, whose parity is measured against the fp64 oracle (1e-3 rel-L2).
+// the overlap-add CZT kernels; tests/test_czt_parity_gpu.py holds them per plane to 4 x the fp32
+// floor + 16 x 2^-24 x the largest residual phase (16: the roundings on the way to sincos_hw).
 __device__ __forceinline__ float2 rs_kernel_fast(float x, float y, float z, float k, const RsPhase& ph) {
   const float rho2 = x * x + y * y;
   const float r2 = rho2 + z * z;

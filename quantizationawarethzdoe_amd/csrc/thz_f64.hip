@@ -761,8 +761,9 @@ static int czt_args(const thz_czt_desc64* d, CztArgs* a, size_t* total) {
   };
   // x_out = linspace(-outH dxo/2, outH dxo/2, outH), y_out likewise (Props/CZT_Prop.py:101-102)
   const double xo = d->outH * d->odx / 2.0, yo = d->outW * d->ody / 2.0;
-  make(&a->pa, d->W, d->outH, -xo, xo);  // the reference's second Bluestein (:246): fx, outH
-  make(&a->pb, d->H, d->outW, -yo, yo);  // its first (:243): fy, outW
+  // a one-point linspace is its start: x_out[-1] = x_out[0] = -xo, so M = 1 zooms onto f2 = f1
+  make(&a->pa, d->W, d->outH, -xo, d->outH == 1 ? -xo : xo);  // the reference's second Bluestein (:246): fx, outH
+  make(&a->pb, d->H, d->outW, -yo, d->outW == 1 ? -yo : yo);  // its first (:243): fy, outW
   // mp a power of two: the reference raises there (see thz_czt.hip czt_validate)
   if (a->pa.np2 == a->pa.m + a->pa.M - 1 || a->pb.np2 == a->pb.m + a->pb.M - 1)
     return fail(THZ_E_ARG, "CZT Bluestein length m + M - 1 is a power of two: the reference's slice "

@@ -141,6 +141,17 @@ def test_slice_vs_oracle_and_planes(geo):
     assert torch.equal(centre, prop.propagate_zx(field, list(ZS), row=out // 2, **_grid(geo)))
 
 
+def test_slice_of_a_one_point_output():
+    """outH = outW = 1: the output grid is a one-point linspace, its start, so both zoom ranges are
+    f2 = f1 (csrc/thz_czt.hip czt_slice_layout, as czt_layout); the only row, against the oracle and
+    the planes.  (With f2 = -f1 the chirp rate is off by 2 pi odx dx / (lambda z) and the result by O(1).)"""
+    geo = (37, 53, 1, 2, 2, (0.25e-3, 0.3e-3), (0.1e-3, 0.12e-3))
+    prop, field = _prop(), _field(geo)
+    got, n = _native_launches(lambda: prop.propagate_zx(field, list(ZS), row=0, **_grid(geo)))
+    assert n == 1 and got.shape == (len(ZS), 2, 2, 1)
+    _check(geo, ZS, 0, got.cpu())
+
+
 def test_compile_time_2048_point_plan():
     zs = ZS[::2]
     prop, field = _prop(), _field(BIG)

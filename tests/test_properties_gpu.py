@@ -10,6 +10,11 @@ that hold for every input:
 
 Tolerances: fp32 rel 1e-5 for the identities (one fp32 pipeline each way); vs the fp64 oracle
 max(1e-4 (1 + k|z| / 1e3), 1.25 x the reference's own fp32 error on the drawn case); fp64 1e-12.
+The fp32 CZT draws (both CZT tests) are value-checked twice: the whole call against the fp64 oracle
+within the same max(1e-4 (1 + k|z| / 1e3), 1.25 x the reference's own fp32 error) -- the loose net --
+and every (b, c) plane against the fp64 reference on the float32 grids within MARGIN x floor32 + PH on
+relative L2 and max|err| / rms (tests/czt_ref.py, the bound of tests/test_czt_parity_gpu.py: about
+1e-6 plus the fp32 rounding of the residual RS phase of the drawn geometry).
 Examples are derandomized, but which ones run can still differ between runs (hypothesis'
 generation depends on more than the seed), so every bound must hold for any draw.
 """
@@ -235,6 +240,37 @@ def test_czt_linearity_and_adjoint(case):
     lhs = torch.vdot(out.detach().reshape(-1).to(torch.complex128), g.reshape(-1).to(torch.complex128))
     rhs = torch.vdot(x.reshape(-1).to(torch.complex128), gx.reshape(-1).to(torch.complex128))
     assert abs(complex(lhs - rhs)) <= 100 * tol * abs(complex(lhs))
+    if not case["f64"]:
+        _czt_values(A(x), x, [float(lam32[0])], (0.5e-3, 0.6e-3), case["z"], M, 0.4e-3)
+
+
+def _czt_values(Ax, x, lam, sp, z, M, od):
+    """A(x) of a drawn fp32 CZT case against the oracle in fp64 within max(1e-4 (1 + k|z| / 1e3), 1.25 x
+    the reference's own fp32 error on the draw), and every (b, c) plane within MARGIN x floor32 + PH of the fp64
+    reference on the float32 grids (tests/czt_ref.py; the bound of tests/test_czt_parity_gpu.py, its
+    roundings count taken per pass from the form make_pass gives the drawn sizes)."""
+    from tests import czt_ref as cr
+    H, W = x.shape[-2:]
+    xc = x.cpu()
+    lam32 = torch.tensor(lam, dtype=torch.float32)
+    sp32 = torch.tensor(sp, dtype=torch.float32)
+    od32, z32 = cr.f32(od), cr.f32(z)
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        ref = orc.czt_forward(xc.to(torch.complex128), lam32.double(), sp32.double(), z32, M, M, od32, od32)
+    finally:
+        torch.set_default_dtype(prev)
+    e = float((Ax.detach().cpu().to(torch.complex128) - ref).norm() / ref.norm())
+    floor = 1e-4 * (1 + abs(z32) * 2 * np.pi / float(lam32.min()) / 1e3)   # the phase-scaled rule of test_asm_properties
+    if e > floor:  # only then does the reference's own fp32 error decide
+        ref32 = orc.czt_forward(xc, lam32, sp32, torch.tensor(z32, dtype=torch.float32), M, M,
+                                torch.tensor(od32, dtype=torch.float32), torch.tensor(od32, dtype=torch.float32))
+        e32 = float((ref32.to(torch.complex128) - ref).norm() / ref.norm())
+        assert e <= 1.25 * e32, (e, e32)
+    geo = cr.Case(H, W, M, sp[0], sp[1], od, od, z, lam)
+    ok, ratio, what = cr.plane_bounds_hold(geo, Ax.detach().cpu(), xc, (cr.pass_form(W, M), cr.pass_form(H, M)))
+    assert ok, (ratio, what)
 
 
 @SETTINGS
@@ -261,7 +297,8 @@ def test_czt_overlap_add_linearity_and_adjoint(case):
         f = ElectricField(x, wavelengths=lam if C > 1 else lam[0], spacing=[0.5e-3, 0.5e-3], device=_dev())
         return prop(f, M, M, od, od).data
 
-    x, y = _rand(rng, (1, C, H, W), torch.complex64), _rand(rng, (1, C, H, W), torch.complex64)
+    B = 2 if 2 * C * H * W <= 3 * 2100 * 2100 else 1  # two batch planes while the call stays within 1 x 3 x 2100^2
+    x, y = _rand(rng, (B, C, H, W), torch.complex64), _rand(rng, (B, C, H, W), torch.complex64)
     lin = A(2 * x - 1j * y)
     ref = 2 * A(x) - 1j * A(y)
     assert float((lin - ref).norm() / ref.norm()) <= 1e-5
@@ -273,6 +310,7 @@ def test_czt_overlap_add_linearity_and_adjoint(case):
     rhs = torch.vdot(x.reshape(-1).to(torch.complex128), gx.reshape(-1).to(torch.complex128))
     scale = max(float(out.detach().norm()) * float(g.norm()), float(x.norm()) * float(gx.norm()))
     assert abs(complex(lhs - rhs)) <= 1e-5 * scale, (abs(complex(lhs - rhs)), scale)
+    _czt_values(out, x, lam, (0.5e-3, 0.5e-3), case["z"], M, od)
 
 
 @SETTINGS

@@ -30,7 +30,7 @@ keeps only a few columns: the thin row-pass carriers run without one.)
 
 Uniform sweeps that take the plane recurrence are not here: they advance H by a product, on purpose,
 and tests/test_asm_recurrence_gpu.py owns their 2e-5 bound.  The CZT forms its chirps in-kernel and
-exports no table: out of scope.
+exports no table: tests/test_czt_parity_gpu.py holds it to the same margin against tests/czt_ref.py.
 """
 import functools
 import os
