@@ -30,9 +30,12 @@ import math
 
 import torch
 
+from tests import parity
+from tests.gpu_util import white_cpu
+from tests.parity import MARGIN, U32, errors
+
 C128 = torch.complex128
 C64 = torch.complex64
-U32 = 2.0 ** -24   # one fp32 rounding, relative
 
 
 def f32(v):
@@ -183,22 +186,12 @@ def czt_forward(x, lam, spacing, z, M, odx, ody, grids="fp32", dtype=C128):
 # ---------------------------------------------------------------------------------------------
 # metrics, the fp32 floor and the bound
 # ---------------------------------------------------------------------------------------------
-def errors(got, ref):
-    """(relative L2, max|err| / rms(ref)) of one plane, both taken in complex128 (tests/table_ref.py)"""
-    got, ref = got.to(C128), ref.to(C128)
-    err = (got - ref).abs()
-    rms = float(ref.abs().pow(2).mean().sqrt())
-    return float(err.pow(2).sum().sqrt() / ref.abs().pow(2).sum().sqrt()), float(err.max()) / rms
-
-
 def floor_of(lo, ref):
     """errors() of the complex64 run ``lo`` against the complex128 run ``ref`` of one plane, checked to
     be what a bound may rest on: positive and below 1e-5 on both metrics.  A plane of one or two
     elements is a single draw of the rounding error and can land under one rounding by chance (3.7e-8
     at M = 1); no fp32 pipeline is expected to, so each figure is at least 2^-24."""
-    rel, mx = errors(lo, ref)
-    assert 0 < rel < 1e-5 and 0 < mx < 1e-5, f"floor32 {rel:.3e} {mx:.3e} is not an fp32 pipeline's error"
-    return max(rel, U32), max(mx, U32)
+    return parity.floor_of(lo, ref, rel_cap=1e-5, max_cap=1e-5, at_least_u32=True)
 
 
 def pass_form(m, M):
@@ -224,9 +217,6 @@ def plane_bounds_hold(case, got, x, forms):
             if r > worst[0]:
                 worst = (r, f"b{b} c{c} err {err[0]:.3e} {err[1]:.3e} bound {bnd[0]:.3e} {bnd[1]:.3e}")
     return worst[0] <= 1, worst[0], worst[1]
-
-
-MARGIN = 4.0   # tests/test_table_parity_gpu.py: a different but equally valid fp32 FFT
 
 
 def bound(floor, ph):
@@ -267,9 +257,7 @@ def row_id(row):
     return f"{row[0]}x{row[1]}_M{row[2]}_B{row[3]}C{row[4]}"
 
 
-def white(shape, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, dtype=C128, generator=g).to(C64)
+white = white_cpu
 
 
 def wavelengths(C):

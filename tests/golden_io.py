@@ -1,4 +1,5 @@
 """Load the committed golden fixtures (produced by tests/golden/gen_golden.py)."""
+import contextlib
 import json
 import os
 
@@ -40,3 +41,33 @@ def rel_l2(a, b):
     a = np.asarray(a, dtype=np.complex128)
     b = np.asarray(b, dtype=np.complex128)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
+
+
+@contextlib.contextmanager
+def replay_draws(layer, A, steps, kinds):
+    """Feed the recorded exponential_ / rand_like draws of each step to the layer in order."""
+    expo, unif = [], []
+    for s in range(steps):
+        for i, k in enumerate(kinds[s]):
+            (expo if k == "expo" else unif).append(A[f"step{s}__draw{i}"])
+    expo.reverse()
+    unif.reverse()
+    orig = torch.rand_like
+
+    def fake_unif(t, *a, **kw):
+        v = unif.pop()
+        assert tuple(t.shape) == v.shape
+        return torch.from_numpy(v).to(device=t.device, dtype=t.dtype)
+
+    def fake_expo(shape, like):
+        v = expo.pop()
+        assert tuple(shape) == v.shape
+        return torch.from_numpy(v).to(like.device)
+
+    layer._gumbel_noise = fake_expo
+    torch.rand_like = fake_unif
+    try:
+        yield
+    finally:
+        torch.rand_like = orig
+    assert not expo and not unif, "not every recorded draw was consumed"

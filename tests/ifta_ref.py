@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from oracle import thz_oracle as orc
+from tests.gpu_util import f32 as _f32
 
 BASE = 2e-3  # BASE_PLANE_THICKNESS as the float32 the kernels hold
 
@@ -149,10 +150,6 @@ def decision_margin(res, lut, hm, q):
 
 
 # ---- the propagation ----------------------------------------------------------------------------------
-def _f32(v):
-    return float(np.float32(v))
-
-
 def asm_planes(field, wavelength, spacing, zs, padding_scale):
     """[Z, 1, 1, H, W]: the oracle's ASM of field [1, 1, H, W] to every z."""
     rd = real_dtype(field)

@@ -16,6 +16,9 @@ oracle on the oracle's own fp64 tables.
 """
 import torch
 
+from tests import parity
+from tests.parity import errors  # noqa: F401  (the metric, under the name this module's callers use)
+
 C128 = torch.complex128
 
 
@@ -160,23 +163,11 @@ def vrs_adjoint_from_table(g, K, dx, dy, z, H, W, dtype=C128):
 # ---------------------------------------------------------------------------------------------
 # metrics and the fp32 floor
 # ---------------------------------------------------------------------------------------------
-def errors(got, ref):
-    """(relative L2, max|err| / rms(ref)) of ``got`` against ``ref``, both taken in complex128.  The
-    second is elementwise: one wrong element of n carries 1 / sqrt(n) of a relative L2 and all of
-    this one."""
-    got, ref = got.to(C128), ref.to(C128)
-    err = (got - ref).abs()
-    rms = float(ref.abs().pow(2).mean().sqrt())
-    return float(err.pow(2).sum().sqrt() / ref.abs().pow(2).sum().sqrt()), float(err.max()) / rms
-
-
 def floor_of(lo, ref):
     """errors() of a complex64 run ``lo`` of the algebra against its complex128 run ``ref``, checked to
     be what a bound may rest on: an fp32 FFT pipeline is no better than one rounding (2^-24) and a few
     tens of them at the very most for transforms of up to 2^28 points."""
-    rel, mx = errors(lo, ref)
-    assert 2.0 ** -24 <= rel <= 2e-6 and rel <= mx <= 2e-5, f"floor32 {rel:.3e} {mx:.3e} is not an fp32 FFT's error"
-    return rel, mx
+    return parity.floor_of(lo, ref, rel_cap=2e-6, max_cap=2e-5)
 
 
 def floor32(fn, *args, ref=None, **kw):

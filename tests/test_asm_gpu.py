@@ -13,14 +13,11 @@ import torch
 
 from oracle import thz_oracle as orc
 from tests.golden_io import GOLDEN, arrays, manifest, rel_l2, spacing, wavelengths
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
 M = manifest()
 C0 = 2.998e8
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _prop_cls():

@@ -17,6 +17,8 @@ of two, the only kind the slice kernels serve), P = 300 (mixed radix), P = 48 (r
 import pytest
 import torch
 
+from tests.gpu_util import launches, white_gpu
+
 pytestmark = pytest.mark.gpu
 
 C0 = 2.998e8
@@ -30,23 +32,13 @@ def _zs(Z):
 
 
 def _white(*shape):
-    g = torch.Generator(device="cuda:0").manual_seed(7)
-    return torch.randn(*shape, dtype=torch.complex64, device="cuda:0", generator=g)
+    return white_gpu(shape, 7)
 
 
-def _launches(call):
+def _timers_run(call):
     """{timer: launches} of one call, the timers that did not run left out."""
-    from quantizationawarethzdoe_amd import _lib
-    _lib.timing_enable(True)
-    try:
-        _lib.timing_reset()
-        call()
-        torch.cuda.synchronize()
-        counts = {name: _lib.timing_read(name)[1] for name in TIMERS}
-    finally:
-        _lib.timing_enable(False)
-        _lib.timing_reset()
-    return {k: v for k, v in counts.items() if v}
+    _, counts = launches(lambda: (call(), torch.cuda.synchronize()), TIMERS)
+    return {k: v for k, v in zip(TIMERS, counts) if v}
 
 
 def _planes(k1, k2, k3):
@@ -68,7 +60,7 @@ def test_forward_planes(case):
     N, pad, Z, zc, want, _ = PLANES[case]
     dx = 0.25e-3 if N == 512 else 1e-3
     x = _white(1, 1, N, N)
-    got = _launches(lambda: P.asm_apply(x, LAM, (dx, dx), _zs(Z), pad, pad, True, 1, False, z_chunk=zc))
+    got = _timers_run(lambda: P.asm_apply(x, LAM, (dx, dx), _zs(Z), pad, pad, True, 1, False, z_chunk=zc))
     assert got == want
 
 
@@ -78,7 +70,7 @@ def test_z_summing_adjoint(case):
     N, pad, Z, zc, _, want = PLANES[case]
     dx = 0.25e-3 if N == 512 else 1e-3
     g = _white(Z, 1, 1, N, N)
-    got = _launches(lambda: P.asm_apply(g, LAM, (dx, dx), _zs(Z), pad, pad, True, 1, True, z_chunk=zc))
+    got = _timers_run(lambda: P.asm_apply(g, LAM, (dx, dx), _zs(Z), pad, pad, True, 1, True, z_chunk=zc))
     assert got == want
 
 
@@ -86,7 +78,7 @@ def test_slice_forward():
     """Z = 70 planes at the default z-chunk (64): two column / row launches behind one K1."""
     from quantizationawarethzdoe_amd import propagation as P
     x = _white(1, 1, 512, 512)
-    got = _launches(lambda: P.asm_slice_apply(x, LAM, (0.25e-3, 0.25e-3), _zs(70), 200, 256, 256, True, 1))
+    got = _timers_run(lambda: P.asm_slice_apply(x, LAM, (0.25e-3, 0.25e-3), _zs(70), 200, 256, 256, True, 1))
     assert got == {"asm_rows_fwd": 1, "asm_cols_slice": 2, "asm_rows_slice": 2}
 
 
@@ -94,7 +86,7 @@ def test_slice_adjoint():
     """The column pass segments the 70 planes itself: one launch of each stage."""
     from quantizationawarethzdoe_amd import propagation as P
     g = _white(70, 1, 1, 512)
-    got = _launches(lambda: P.asm_slice_adjoint(g, LAM, (0.25e-3, 0.25e-3), _zs(70), 200, 256, 256, True, 1, 512))
+    got = _timers_run(lambda: P.asm_slice_adjoint(g, LAM, (0.25e-3, 0.25e-3), _zs(70), 200, 256, 256, True, 1, 512))
     assert got == {"asm_rows_fwd": 1, "asm_cols_slice_adj": 1, "asm_rows_inv": 1}
 
 
@@ -103,12 +95,12 @@ def test_mixed_radix_fused_loss():
     from quantizationawarethzdoe_amd import propagation as P
     x = _white(1, 1, 100, 100)
     target = torch.rand(1, 1, 100, 100, device="cuda:0")
-    got = _launches(lambda: P.asm_propagate_loss(x, target, LAM, (1e-3, 1e-3), 0.05, 100, 100))
+    got = _timers_run(lambda: P.asm_propagate_loss(x, target, LAM, (1e-3, 1e-3), 0.05, 100, 100))
     assert got == _planes(1, 1, 1)
 
 
 def test_rsc():
     from quantizationawarethzdoe_amd import propagation as P
     x = _white(1, 1, 16, 16)
-    got = _launches(lambda: P.rsc_apply(x, LAM, (1e-3, 1e-3), 0.05))
+    got = _timers_run(lambda: P.rsc_apply(x, LAM, (1e-3, 1e-3), 0.05))
     assert got == {"rsc_kernel_fft": 1, "asm_rows_fwd": 1, "asm_cols": 1, "asm_rows_inv": 1}

@@ -34,6 +34,7 @@ import torch
 
 from oracle import thz_oracle as orc
 from tests.golden_io import rel_l2
+from tests.gpu_util import f32 as _f32
 
 pytestmark = pytest.mark.gpu
 C0 = 2.998e8
@@ -47,10 +48,6 @@ NONUNIFORM3 = [0.02, 0.05, 0.11]                  # the column pass's per-plane 
 # as the 4-plane sweep does here.  48 planes leave every range 4 or more.
 UNIFORM48 = [0.03 + 0.002 * k for k in range(48)]
 _X = {}
-
-
-def _f32(v):
-    return float(np.float32(v))
 
 
 def _field(seed, shape=(1, 1, N, N)):

@@ -19,20 +19,15 @@ import pytest
 import torch
 
 from tests import table_ref as tr
-from tests import test_table_parity_gpu as tp
+from tests.gpu_util import f32, lam_ghz, white_gpu
+from tests import table_cases as tp
 
 pytestmark = pytest.mark.gpu
-C0 = 2.998e8
 SENTINEL = complex(-7.25, 3.5)
 
 
 def _white(shape, seed, channels=1):
-    dev = torch.device("cuda:0")
-    g = torch.Generator(device=dev).manual_seed(seed)
-    x = torch.randn(*shape, dtype=torch.complex64, device=dev, generator=g)
-    lam = [float(torch.tensor(C0 / (f * 1e9), dtype=torch.float32)) for f in (300, 280)[:channels]]
-    sp = [float(torch.tensor(0.25e-3, dtype=torch.float32))] * 2
-    return x, lam, sp
+    return white_gpu(shape, seed), [lam_ghz(f) for f in (300, 280)[:channels]], [f32(0.25e-3)] * 2
 
 
 def _both_forms(x, lam, sp, zs, ph, pw, extra_rows=0):
@@ -103,7 +98,7 @@ def test_pair_b64_8192_other_crop():
 def test_pair_b64_1024_against_the_table_algebra():
     """The pair form alone against complex128 algebra on its own exported table (9 rows: odd Hout)."""
     from quantizationawarethzdoe_amd import _lib
-    a = tp._Asm(H=9, W=512, s=1, bl=None, z=0.05)
+    a = tp.AsmCase(H=9, W=512, s=1, bl=None, z=0.05)
     assert a.Pw == 1024
     try:
         _lib.asm_row_pairs(1)
@@ -114,4 +109,4 @@ def test_pair_b64_1024_against_the_table_algebra():
     ref = tr.asm_from_table(a.x, Hc, a.ph, a.pw, a.unpad)
     assert out.shape == ref.shape
     floor = tr.floor32(tr.asm_from_table, a.x, Hc, a.ph, a.pw, a.unpad, ref=ref)
-    tp._judge("asm-rows-pair", "9x512 s1 Pw1024 none, pairs", out, ref, floor)
+    tp.judge("asm-rows-pair", "9x512 s1 Pw1024 none, pairs", out, ref, floor)

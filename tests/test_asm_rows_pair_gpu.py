@@ -21,9 +21,9 @@ import torch
 
 from oracle import thz_oracle as orc
 from tests.golden_io import rel_l2
+from tests.gpu_util import f32, lam_ghz, white_gpu
 
 pytestmark = pytest.mark.gpu
-C0 = 2.998e8
 
 
 def _both_forms(x, lam, sp, zs, s, **kw):
@@ -43,12 +43,7 @@ def _both_forms(x, lam, sp, zs, s, **kw):
 
 
 def _white(shape, seed):
-    dev = torch.device("cuda:0")
-    g = torch.Generator(device=dev).manual_seed(seed)
-    x = torch.randn(*shape, dtype=torch.complex64, device=dev, generator=g)
-    lam = [float(torch.tensor(C0 / 300e9, dtype=torch.float32))]
-    sp = [float(torch.tensor(0.25e-3, dtype=torch.float32))] * 2
-    return x, lam, sp
+    return white_gpu(shape, seed), [lam_ghz(300)], [f32(0.25e-3)] * 2
 
 
 def _assert_bit_identical(one, two):
@@ -101,7 +96,7 @@ def test_pair_generic_1024_odd_rows_bit_identical_and_vs_oracle():
 def test_pair_2048_z_chunks_bit_identical():
     """C: Pw = 2048, Hout = 64, three planes in z-chunks of two (the second launch has zoff = 2)."""
     x, lam, sp = _white((1, 2, 64, 1024), 14)
-    lam = lam + [float(torch.tensor(C0 / 280e9, dtype=torch.float32))]
+    lam = lam + [lam_ghz(280)]
     one, two = _both_forms(x, lam, sp, [0.03, 0.06, 0.09], 1, z_chunk=2)
     assert two.shape == (3, 1, 2, 64, 1024)
     _assert_bit_identical(one, two)

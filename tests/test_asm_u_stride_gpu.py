@@ -23,20 +23,14 @@ import torch
 
 from oracle import thz_oracle as orc
 from tests.golden_io import rel_l2
+from tests.gpu_util import f32 as _f32, white_gpu
 
 pytestmark = pytest.mark.gpu
 C0 = 2.998e8
 
 
-def _f32(v):
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
 def _white(shape, seed, freqs=(300e9,), dx=0.25e-3):
-    dev = torch.device("cuda:0")
-    g = torch.Generator(device=dev).manual_seed(seed)
-    x = torch.randn(*shape, dtype=torch.complex64, device=dev, generator=g)
-    return x, [_f32(C0 / f) for f in freqs], [_f32(dx)] * 2
+    return white_gpu(shape, seed), [_f32(C0 / f) for f in freqs], [_f32(dx)] * 2
 
 
 def _assert_planes_vs_oracle(planes, x, lam, sp, zs, s):

@@ -3,8 +3,11 @@ without a GPU: the symbols are exported, the ABI version matches the bindings, a
 validation path returns its code and leaves a message in thz_last_error() before any device call.
 """
 import ctypes
+import functools
 
 import pytest
+
+from tests.gpu_util import workspace_size
 
 
 def _desc(H=512, W=512, pad=256, unpad=True, Z=3, **kw):
@@ -23,11 +26,7 @@ def _forward(d, row, inp=8, out=8, ws=8, ws_bytes=1 << 40):
     return code, _lib.lib().thz_last_error().decode()
 
 
-def _size(d):
-    from quantizationawarethzdoe_amd import _lib
-    n = ctypes.c_size_t(0)
-    code = _lib.lib().thz_asm_slice_workspace_size(ctypes.byref(d), ctypes.byref(n))
-    return code, n.value, _lib.lib().thz_last_error().decode()
+_size = functools.partial(workspace_size, "thz_asm_slice_workspace_size")
 
 
 def test_symbols_exported_and_abi_9():

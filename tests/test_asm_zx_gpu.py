@@ -17,20 +17,11 @@ import torch
 
 from oracle import thz_oracle as orc
 from tests.golden_io import rel_l2
+from tests.gpu_util import lam_ghz as _lam, white_gpu as _white
 
 pytestmark = pytest.mark.gpu
-C0 = 2.998e8
 DX = float(torch.tensor(0.25e-3, dtype=torch.float32))
 SWEEP40 = [float(v) for v in torch.linspace(20e-3, 120e-3, 40, dtype=torch.float64)]
-
-
-def _lam(ghz):
-    return float(torch.tensor(C0 / (ghz * 1e9), dtype=torch.float32))
-
-
-def _white(shape, seed, dtype=torch.complex64):
-    g = torch.Generator(device="cuda:0").manual_seed(seed)
-    return torch.randn(*shape, dtype=dtype, device="cuda:0", generator=g)
 
 
 def _field(x, ghz=(300,), sp=(DX, DX)):

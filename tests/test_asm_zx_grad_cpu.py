@@ -5,8 +5,11 @@ call, the workspace holds one plane's gradient spectrum and the rows' spectra on
 propagate_zx refuses an unknown ``grad`` before anything touches a device.
 """
 import ctypes
+import functools
 
 import pytest
+
+from tests.gpu_util import workspace_size
 
 LAM, DX = 2.998e8 / 300e9, 0.25e-3
 
@@ -30,11 +33,7 @@ def _adjoint(d, row, gout=8, gin=8, ws=8, ws_bytes=1 << 40):
     return code, _lib.lib().thz_last_error().decode()
 
 
-def _size(d):
-    from quantizationawarethzdoe_amd import _lib
-    n = ctypes.c_size_t(0)
-    code = _lib.lib().thz_asm_slice_adjoint_workspace_size(ctypes.byref(d), ctypes.byref(n))
-    return code, n.value, _lib.lib().thz_last_error().decode()
+_size = functools.partial(workspace_size, "thz_asm_slice_adjoint_workspace_size")
 
 
 def test_symbols_exported_bound_and_abi_still_9():

@@ -3,13 +3,9 @@
 import pytest
 import torch
 
+from tests.gpu_util import dev as _dev
+
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda:0")
 
 
 def test_stream_handle_is_the_current_stream():

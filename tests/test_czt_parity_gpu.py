@@ -43,12 +43,12 @@ counts of csrc/thz_czt.hip's timers czt_rows / czt_rows_blk / czt_cols / czt_col
 
 Each case prints its lines (worst plane per metric); THZ_CZT_PARITY_LOG=<file> appends them to a file.
 """
-import os
-
 import pytest
 import torch
 
 from tests import czt_ref as cr
+from tests.gpu_util import dev as _dev, launches
+from tests.parity import emit
 
 pytestmark = pytest.mark.gpu
 TIMERS = ("czt_rows", "czt_rows_blk", "czt_cols", "czt_cols_blk", "czt_adjoint")
@@ -57,22 +57,6 @@ CASES = [(r, g) for r in cr.ROWS for g in cr.GEOMETRIES]
 
 def _id(v):
     return cr.row_id(v) if isinstance(v, tuple) else v
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _launches(fn):
-    """(result of fn(), launches of each timer of TIMERS)"""
-    from quantizationawarethzdoe_amd import _lib
-    _lib.timing_enable(True)
-    try:
-        _lib.timing_reset()
-        out = fn()
-        return out, tuple(_lib.timing_read(n)[1] for n in TIMERS)
-    finally:
-        _lib.timing_enable(False)
 
 
 def _judge(what, name, got, ref, lo, ph):
@@ -96,11 +80,7 @@ def _judge(what, name, got, ref, lo, ph):
         lines.append(f"czt-parity {what:<8s} {name:<32s} {metric:<7s} worst plane b{b} c{c}  floor32 {fl:.3e}  PH {p:.3e}"
                      f"  err {e:.3e}  bound {bn:.3e}  err/bound {ratio:5.3f}")
     for line in lines:
-        print(line)
-    log = os.environ.get("THZ_CZT_PARITY_LOG")
-    if log:
-        with open(log, "a") as f:
-            f.write("".join(line + "\n" for line in lines))
+        emit("THZ_CZT_PARITY_LOG", line)
     assert worst[0][0] <= 1 and worst[1][0] <= 1, "\n".join(lines)
 
 
@@ -128,10 +108,10 @@ def test_czt_forward_and_backward(row, geo):
     case, x, g = cr.build(row, geo)
     name = f"{cr.row_id(row)} {geo}"
     xd = x.to(_dev()).requires_grad_(True)
-    out, n = _launches(lambda: _prop(_field(xd, C, geo), M, geo))
+    out, n = launches(lambda: _prop(_field(xd, C, geo), M, geo), TIMERS)
     # the form each pass took: one launch per pass, the overlap-add ones also under their own names
     assert n == (1, int(fa == cr.BLK), 1, int(fb == cr.BLK), 0), (n, fa, fb)
-    gin, n = _launches(lambda: torch.autograd.grad(out, xd, grad_outputs=g.to(_dev()))[0])
+    gin, n = launches(lambda: torch.autograd.grad(out, xd, grad_outputs=g.to(_dev()))[0], TIMERS)
     assert n == (0, 0, 0, 0, 1), n   # the adjoint: the np2 kernels whatever the forward took
     ref, ref_g = case.grad(x, g)
     lo, lo_g = case.grad(x, g, cr.C64)

@@ -4,10 +4,13 @@ a message in thz_last_error() before any device call, the workspace holds a chun
 column sums only, and the decomposition the kernels implement equals the oracle's planes in fp64.
 """
 import ctypes
+import functools
 import math
 
 import pytest
 import torch
+
+from tests.gpu_util import workspace_size
 
 # (H, W, out, C, B, (dx, dy), (odx, ody)): the geometries of tests/test_czt_zx_gpu.py
 GEOMETRIES = [
@@ -34,11 +37,7 @@ def _forward(d, inp=8, out=8, ws=8, ws_bytes=1 << 40):
     return code, _lib.lib().thz_last_error().decode()
 
 
-def _size(d):
-    from quantizationawarethzdoe_amd import _lib
-    n = ctypes.c_size_t(0)
-    code = _lib.lib().thz_czt_slice_workspace_size(ctypes.byref(d), ctypes.byref(n))
-    return code, n.value, _lib.lib().thz_last_error().decode()
+_size = functools.partial(workspace_size, "thz_czt_slice_workspace_size")
 
 
 def test_symbols_exported_and_abi_9():

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from oracle import thz_oracle as orc
+from tests.gpu_util import dev as _dev, f32 as _f32
 
 pytestmark = pytest.mark.gpu
 
@@ -30,15 +31,7 @@ ZS = (0.030, 0.041, 0.055, 0.0725, 0.090)   # 30 ... 90 mm, not uniformly spaced
 ORACLE_TOL, PLANES_TOL = 1e-3, 2e-3
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _f32(v):
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
-def _lam(C):
+def _synthetic_lam(C):
     return [1e-3 * (1 + 0.1 * c) for c in range(C)]
 
 
@@ -59,7 +52,7 @@ def _field(geo, dtype=torch.complex64, grad=False):
     data = _input(geo, dtype).to(_dev())
     if grad:
         data.requires_grad_(True)
-    wl = _lam(C)
+    wl = _synthetic_lam(C)
     if dtype == torch.complex128:
         wl = torch.tensor(wl, dtype=torch.float64)
     elif C == 1:
@@ -89,7 +82,7 @@ def _oracle_planes(geo, zs, exact=False):
     torch.set_default_dtype(torch.float64)
     try:
         x = _input(geo, torch.complex128 if exact else torch.complex64).to(torch.complex128)
-        lam = torch.tensor([r(v) for v in _lam(C)])
+        lam = torch.tensor([r(v) for v in _synthetic_lam(C)])
         return torch.stack([orc.czt_forward(x, lam, [r(spacing[0]), r(spacing[1])], r(z), out, out, r(odx), r(ody))
                             for z in zs])
     finally:

@@ -5,10 +5,13 @@ chunk's tables and T only, and the two-step adjoint the kernels implement (line 
 written out explicitly in torch fp64, equals autograd through the oracle's planes.
 """
 import ctypes
+import functools
 import math
 
 import pytest
 import torch
+
+from tests.gpu_util import workspace_size
 
 # (H, W, out, C, B, (dx, dy), (odx, ody)): the geometries of tests/test_czt_zx_cpu.py
 GEOMETRIES = [
@@ -36,11 +39,7 @@ def _adjoint(d, g=8, gin=8, ws=8, ws_bytes=1 << 40):
     return code, _lib.lib().thz_last_error().decode()
 
 
-def _size(d):
-    from quantizationawarethzdoe_amd import _lib
-    n = ctypes.c_size_t(0)
-    code = _lib.lib().thz_czt_slice_adjoint_workspace_size(ctypes.byref(d), ctypes.byref(n))
-    return code, n.value, _lib.lib().thz_last_error().decode()
+_size = functools.partial(workspace_size, "thz_czt_slice_adjoint_workspace_size")
 
 
 def test_symbols_exported_bound_and_abi_still_9():

@@ -21,6 +21,7 @@ import pytest
 import torch
 
 from oracle import thz_oracle as orc
+from tests.gpu_util import dev as _dev, f32 as _f32, launches
 
 pytestmark = pytest.mark.gpu
 
@@ -37,15 +38,7 @@ ORACLE_TOL, PLANES_TOL, IDENTITY_TOL, F64_TOL = 1e-3, 2e-3, 1e-5, 1e-8
 IDS = dict(ids=lambda g: f"{g[0]}x{g[1]}to{g[2]}")
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _f32(v):
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
-def _lam(C):
+def _synthetic_lam(C):
     return [1e-3 * (1 + 0.1 * c) for c in range(C)]
 
 
@@ -75,7 +68,7 @@ def _field(geo, dtype=torch.complex64, grad=False, data=None):
         data = _input(geo, dtype).to(_dev())
         if grad:
             data.requires_grad_(True)
-    wl = _lam(C)
+    wl = _synthetic_lam(C)
     if dtype == torch.complex128:
         wl = torch.tensor(wl, dtype=torch.float64)
     elif C == 1:
@@ -96,7 +89,7 @@ def _grid(geo):
 def _cfg(geo):
     """(wavelengths, spacing, out, out, odx, ody) as the kernels receive them."""
     H, W, out, C, B, spacing, (odx, ody) = geo
-    return _lam(C), (_f32(spacing[0]), _f32(spacing[1])), out, out, odx, ody
+    return _synthetic_lam(C), (_f32(spacing[0]), _f32(spacing[1])), out, out, odx, ody
 
 
 @functools.lru_cache(maxsize=None)
@@ -113,7 +106,7 @@ def _oracle_grads(geo, zs, rows, exact=False):
     torch.set_default_dtype(torch.float64)
     try:
         x = _input(geo, dt).to(torch.complex128).requires_grad_(True)
-        lam = torch.tensor([r(v) for v in _lam(C)])
+        lam = torch.tensor([r(v) for v in _synthetic_lam(C)])
         acc = {p: torch.zeros(B, C, H, W, dtype=torch.complex128) for p in rows}
         for k, z in enumerate(zs):
             planes = orc.czt_forward(x, lam, spacing, r(z), out, out, r(odx), r(ody))
@@ -134,16 +127,10 @@ def _dot(a, b):
     return complex(torch.vdot(a.reshape(-1).to(torch.complex128), b.reshape(-1).to(torch.complex128)))
 
 
-def _launches(fn, name="czt_slice_expand"):
+def _expand_launches(fn, name="czt_slice_expand"):
     """(result, launches of the expand kernel) of fn(): whether the native backward served the call."""
-    from quantizationawarethzdoe_amd import _lib
-    _lib.timing_enable(True)
-    try:
-        _lib.timing_reset()
-        out = fn()
-        return out, _lib.timing_read(name)[1]
-    finally:
-        _lib.timing_enable(False)
+    out, (n,) = launches(fn, (name,))
+    return out, n
 
 
 def _slice_vjp(geo, zs, row, g, axis="x", cls=None):
@@ -155,7 +142,7 @@ def _slice_vjp(geo, zs, row, g, axis="x", cls=None):
         gx, = torch.autograd.grad(out, f.data, grad_outputs=g)
         return out.detach(), gx
 
-    (out, gx), n = _launches(run)
+    (out, gx), n = _expand_launches(run)
     return out, gx, n
 
 
@@ -223,11 +210,11 @@ def test_public_api_slice_vs_planes(geo):
     row = geo[2] // 2
     g = _cotangent(geo, len(ZS), row).to(_dev())
     f = _field(geo, grad=True)
-    out, n = _launches(lambda: _prop().propagate_zx(f, list(ZS), row=row, grad="slice", **_grid(geo)))
+    out, n = _expand_launches(lambda: _prop().propagate_zx(f, list(ZS), row=row, grad="slice", **_grid(geo)))
     assert out.grad_fn is not None and n == 0   # the forward alone launches no expand kernel
-    gs, n = _launches(lambda: torch.autograd.grad(out, f.data, grad_outputs=g)[0])
+    gs, n = _expand_launches(lambda: torch.autograd.grad(out, f.data, grad_outputs=g)[0])
     assert n == 1, "one expand launch for the five-plane sweep"
-    (want, gp), n = _launches(lambda: _planes_vjp(geo, ZS, row, g))
+    (want, gp), n = _expand_launches(lambda: _planes_vjp(geo, ZS, row, g))
     assert n == 0, "grad='planes' never runs the slice adjoint"
     errs = ((out.detach() - want).flatten(1).norm(dim=1) / want.flatten(1).norm(dim=1)).tolist()
     print(f"czt zx grad api {geo[:3]}: values {max(errs):.3e}, gradient {_rel(gs, gp):.3e}")
@@ -297,7 +284,7 @@ def test_two_backward_calls_are_bit_identical():
 def test_input_that_does_not_require_grad():
     geo, row = GEOMETRIES[0], 7
     f = _field(geo)
-    got, n = _launches(lambda: _prop().propagate_zx(f, list(ZS), row=row, grad="slice", **_grid(geo)),
+    got, n = _expand_launches(lambda: _prop().propagate_zx(f, list(ZS), row=row, grad="slice", **_grid(geo)),
                        "czt_slice_collapse")
     assert n == 1 and got.grad_fn is None and not got.requires_grad
     assert torch.equal(got, _prop().propagate_zx(f, list(ZS), row=row, **_grid(geo)))
@@ -314,7 +301,7 @@ def test_complex128_falls_back_and_is_differentiable():
             out = _prop().propagate_zx(f, list(ZS), row=row, grad="slice", **_grid(geo))
             return out, torch.autograd.grad(out, f.data, grad_outputs=g)[0]
 
-        (out, gx), n = _launches(run)
+        (out, gx), n = _expand_launches(run)
         assert n == 0 and out.dtype == gx.dtype == torch.complex128
         err = _rel(gx, want[row])
         print(f"czt zx grad complex128 row {row}: vs oracle {err:.3e}")
@@ -335,7 +322,7 @@ def test_gradient_reaches_a_phase_parameter():
             zx = _prop().propagate_zx(f, list(ZS), grad=mode, **_grid(geo))
             return torch.autograd.grad(zx.abs().square().sum(), phi)[0]
 
-        grads[mode], n = _launches(run)
+        grads[mode], n = _expand_launches(run)
         assert n == (1 if mode == "slice" else 0)
     err = _rel(grads["slice"], grads["planes"])
     print(f"czt zx grad d phi: slice vs planes {err:.3e}")

@@ -13,15 +13,10 @@ import pytest
 import torch
 
 from tests.golden_io import rel_l2
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
 C0 = 2.998e8
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda:0")
 
 
 def _draw_u(state, stream, hs, ws, dev):

@@ -11,15 +11,11 @@ import math
 import pytest
 import torch
 
+from tests.gpu_util import dev as _dev
+
 pytestmark = pytest.mark.gpu
 C0 = 2.998e8
 MM = 1e-3
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda:0")
 
 
 KINDS = ["FP", "STE", "PSQ", "SGV3_0.1", "SGV3_0.5", "SGV3_0.9", "NGS", "SGV1"]

@@ -23,15 +23,12 @@ from hypothesis import strategies as st
 
 from oracle import thz_oracle as orc
 from tests.golden_io import arrays, manifest, rel_l2, wavelengths
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
 M = manifest()
 C0 = 2.998e8
 MM = 1e-3
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _mods():

@@ -17,13 +17,10 @@ from hypothesis import HealthCheck, given, settings
 from hypothesis import strategies as st
 
 from tests.golden_io import rel_l2
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
 C0 = 2.998e8
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _oracle_loss(ws, u, target, noises, chained):

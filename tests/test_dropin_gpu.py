@@ -10,7 +10,7 @@ import torch
 
 from oracle import thz_oracle as orc
 from tests.golden_io import arrays, manifest, rel_l2
-from tests.test_optics_qat_gpu import replay_draws
+from tests.golden_io import replay_draws
 
 pytestmark = pytest.mark.gpu
 M = manifest()

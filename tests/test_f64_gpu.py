@@ -20,14 +20,11 @@ from hypothesis import HealthCheck, example, given, settings
 from hypothesis import strategies as st
 
 from tests.golden_io import arrays, manifest, rel_l2
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
 M = manifest()
 C0 = 2.998e8
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _wl64(freqs):

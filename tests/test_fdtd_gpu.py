@@ -14,25 +14,20 @@ workgroup's x tile is 256 lanes x 4 = 1024 cells of one row: case (b) has Nx = 1
 """
 import functools
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from tests import fdtd_ref as fr
-from tests import table_ref as tr
+from tests import parity
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 4.0
 LAM = PX = 1e-3
 EPS = 2.66
 FD_TZ = 16
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _heights(H, W, T, delta, seed):
@@ -87,16 +82,8 @@ def _case(name):
 
 
 def _judge(what, name, got, ref, lo):
-    floor = tr.errors(lo, ref)
-    rel, mx = tr.errors(got, ref)
-    line = (f"fdtd-parity {what:<8s} {name:<16s} floor32 {floor[0]:.3e} {floor[1]:.3e}  err {rel:.3e} {mx:.3e}"
-            f"  ratio {rel / floor[0]:5.2f} {mx / floor[1]:5.2f}")
-    print(line)
-    log = os.environ.get("THZ_FDTD_PARITY_LOG")
-    if log:
-        with open(log, "a") as f:
-            f.write(line + "\n")
-    assert floor[0] > 0 and rel <= MARGIN * floor[0] and mx <= MARGIN * floor[1], line
+    """``lo``: the restatement's own float32 run, whose errors are the floor (asserted positive by the judge)"""
+    parity.judge("THZ_FDTD_PARITY_LOG", "fdtd-parity", what, name, got, ref, parity.errors(lo, ref), widths=(8, 16))
 
 
 @pytest.mark.parametrize("name", ["a-2d", "b-ppc5-nx1030", "c-pol-y", "d-lossless", "d-tand0.3"])

@@ -29,17 +29,17 @@ from quantizationawarethzdoe_amd.Components import quantization as Q
 from quantizationawarethzdoe_amd.Components.discrete_doe import DiscreteDOE
 from quantizationawarethzdoe_amd.utils import Helper_Functions as HF
 from tests import heightmap_ref as hr
+from tests.gpu_util import bits as _bits, dev as _dev, place as _place
+from tests.parity import Ratios
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = np.load(os.path.join(ROOT, "tests", "golden", "heightmap_golden.npz"))
 S = {"1": 1.0, "2p5": 2.5, "11": 11.0}
-RATIOS = {}
-
-
-def _dev():
-    return torch.device("cuda:0")
+RATIOS = Ratios("THZ_HEIGHTMAP_PARITY_LOG", "# largest err / bound per quantity; bound = 4 max(e32, 2^-24 |value|) in the maximum norm "
+                "(values), 4 max(e32, 2^-24) (total-variation gradient, relative L2)\n")
+_note = RATIOS.note
 
 
 def _g(name):
@@ -49,44 +49,11 @@ def _g(name):
 @pytest.fixture(scope="module", autouse=True)
 def _ratio_log():
     yield
-    path = os.environ.get("THZ_HEIGHTMAP_PARITY_LOG")
-    if path:
-        with open(path, "w") as fh:
-            fh.write("# largest err / bound per quantity; bound = 4 max(e32, 2^-24 |value|) in the maximum norm "
-                     "(values), 4 max(e32, 2^-24) (total-variation gradient, relative L2)\n")
-            for k in sorted(RATIOS):
-                fh.write(f"{k:28s} {RATIOS[k][0]:.4f}   ({RATIOS[k][1]})\n")
-
-
-def _note(what, case, ratio):
-    print(f"{what:26s} {case:60s} err / bound = {ratio:.4f}")
-    if what not in RATIOS or ratio > RATIOS[what][0]:
-        RATIOS[what] = (ratio, case)
+    RATIOS.write()
 
 
 def _value(what, case, got, r64, r32):
-    got = got.detach().cpu().double()
-    assert got.shape == r64.shape, (got.shape, r64.shape)
-    assert bool(torch.isfinite(got).all())
-    err = float((got - r64).abs().max())
-    e32 = float((r32.double() - r64).abs().max())
-    bound = 4 * max(e32, 2.0 ** -24 * float(r64.abs().max()))
-    _note(what, case, err / bound if bound else float(err > 0))
-    assert err <= bound, (what, case, err, e32, bound)
-
-
-def _bits(a, b):
-    a, b = a.detach().cpu(), b.detach().cpu()
-    return a.dtype == b.dtype and a.shape == b.shape and bool((a.view(torch.int32) == b.view(torch.int32)).all())
-
-
-def _place(t, offset=0):
-    """A contiguous device copy whose pointer is 16-byte aligned (offset 0) or one element past."""
-    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=_dev())
-    v = buf[offset:offset + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert (v.data_ptr() % 16 == 0) == (offset == 0)
-    return v.detach()
+    RATIOS.value(what, case, got, {torch.float64: r64, torch.float32: r32}.get)
 
 
 # ---- quantizer forward -------------------------------------------------------------------------

@@ -22,7 +22,6 @@ Every comparison prints its ratio err / bound; THZ_IFTA_PARITY_LOG=<file> writes
 """
 import functools
 import math
-import os
 
 import pytest
 import torch
@@ -32,10 +31,14 @@ from quantizationawarethzdoe_amd.DataType.ElectricField import ElectricField
 from quantizationawarethzdoe_amd.Props.ASM_Prop import ASM_prop
 from quantizationawarethzdoe_amd.utils import metrics
 from tests import ifta_ref as ir
+from tests.gpu_util import bits as _bits, dev as _dev, place as _place
+from tests.parity import Ratios
 
 pytestmark = pytest.mark.gpu
 
-RATIOS, VALUES = {}, {}
+RATIOS = Ratios("THZ_IFTA_PARITY_LOG", "# largest err / bound per quantity; bounds: sums count 2^-52 |fp64|; project, heights, history "
+                "4 max(e32, 2^-24 |value|), maximum norm; set aside: share of cells, at most 0.01\n", widths=(30, 56, 34))
+_note, VALUES = RATIOS.note, RATIOS.values
 SHAPES = [(1, 1), (37, 53), (64, 256), (130, 1030)]
 LAM, EPS, TAND = 2.998e8 / 300e9, 2.66, 0.03
 HM = ir.h_max(LAM, EPS)
@@ -43,47 +46,10 @@ U24, U52 = 2.0 ** -24, 2.0 ** -52
 LUTS = {1: [0.3e-3], 2: [0.1e-3, 0.9e-3], 4: [0.05e-3, 0.2e-3, 0.9e-3, 1.5e-3], 10: [HM * i / 10 for i in range(10)]}
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
 @pytest.fixture(scope="module", autouse=True)
 def _ratio_log():
     yield
-    path = os.environ.get("THZ_IFTA_PARITY_LOG")
-    if path:
-        with open(path, "w") as fh:
-            fh.write("# largest err / bound per quantity; bounds: sums count 2^-52 |fp64|; project, heights, history "
-                     "4 max(e32, 2^-24 |value|), maximum norm; set aside: share of cells, at most 0.01\n")
-            for k in sorted(RATIOS):
-                fh.write(f"{k:34s} {RATIOS[k][0]:.4f}   ({RATIOS[k][1]})\n")
-            for k in sorted(VALUES):
-                fh.write(f"{k:34s} {VALUES[k]}\n")
-
-
-def _note(what, case, ratio):
-    print(f"{what:30s} {case:56s} err / bound = {ratio:.4f}")
-    if what not in RATIOS or ratio > RATIOS[what][0]:
-        RATIOS[what] = (ratio, case)
-
-
-def _bits(a, b):
-    a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    if a.is_complex():
-        a, b = torch.view_as_real(a), torch.view_as_real(b)
-    wide = torch.int64 if a.element_size() == 8 else torch.int32
-    return bool((a.view(wide) == b.view(wide)).all())
-
-
-def _place(t, offset=0):
-    """A contiguous device copy whose pointer is 16-byte aligned (offset 0) or one element past."""
-    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=_dev())
-    v = buf[offset:offset + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert (v.data_ptr() % 16 == 0) == (offset == 0)
-    return v.detach()
+    RATIOS.write()
 
 
 # ---- inputs and their float64 results, each made once --------------------------------------------------

@@ -14,15 +14,10 @@ import torch
 
 from oracle import thz_oracle as orc
 from tests.golden_io import rel_l2
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
 C0 = 2.998e8
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda:0")
 
 
 # (B, C, H, W, padding_scale, target broadcast): P = 300 mixed-radix (cfg4 / cfg5), power of two,

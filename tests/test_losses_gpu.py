@@ -5,7 +5,7 @@ Bound.  The reference is tests/losses_ref.py in float64 on the CPU (pinned by te
 For every compared quantity
     |kernel - fp64| <= 4 x max(e32, 2^-24 |value|),
 e32 the error of the same restatement in float32 on the CPU on the same input, 4 the project's
-table-parity factor, the floor one rounding of the output.  A quantity with many
+table-parity factor (tests/parity.py), the floor one rounding of the output.  A quantity with many
 elements (a reduction='none' output, a size_average=False vector) is compared in the maximum norm:
 err, e32 and |value| are the maxima over its elements -- an element the float32 sequence happens to
 get exactly must not turn the floor into a per-element demand of one rounding on a map whose every
@@ -15,7 +15,6 @@ element carries several.  Gradients: relative L2 against the float64 autograd of
 Every comparison prints its ratio err / bound; THZ_LOSSES_PARITY_LOG=<file> writes the largest per
 loss there (profiles/losses_parity_ratios.txt is such a run on an MI355X).
 """
-import os
 import warnings
 
 import pytest
@@ -24,60 +23,20 @@ import torch
 from quantizationawarethzdoe_amd import _lib, optics
 from quantizationawarethzdoe_amd.utils import losses as M
 from tests import losses_ref as lr
+from tests.gpu_util import bits as _bits, dev as _dev, place as _place
+from tests.parity import MARGIN, U32, Ratios
 
 pytestmark = pytest.mark.gpu
 
-RATIOS = {}
-
-
-def _dev():
-    return torch.device("cuda:0")
+RATIOS = Ratios("THZ_LOSSES_PARITY_LOG", "# largest err / bound per loss; bound = 4 max(e32, 2^-24 |value|) (values), "
+                "4 max(e32, 1e-6) (gradients, relative L2)\n", widths=(24, 60, 28))
+_value, _grad = RATIOS.value, RATIOS.grad
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _ratio_log():
     yield
-    path = os.environ.get("THZ_LOSSES_PARITY_LOG")
-    if path:
-        with open(path, "w") as fh:
-            fh.write("# largest err / bound per loss; bound = 4 max(e32, 2^-24 |value|) (values), "
-                     "4 max(e32, 1e-6) (gradients, relative L2)\n")
-            for k in sorted(RATIOS):
-                fh.write(f"{k:28s} {RATIOS[k][0]:.4f}   ({RATIOS[k][1]})\n")
-
-
-def _note(loss, case, ratio):
-    print(f"{loss:24s} {case:60s} err / bound = {ratio:.4f}")
-    if loss not in RATIOS or ratio > RATIOS[loss][0]:
-        RATIOS[loss] = (ratio, case)
-
-
-def _value(loss, case, got, fn):
-    """fn(dtype) -> the restatement on the CPU.  Maximum norm over the quantity's elements."""
-    r64, r32 = fn(torch.float64), fn(torch.float32)
-    got = got.detach().cpu().double()
-    assert got.shape == r64.shape, (got.shape, r64.shape)
-    assert bool(torch.isfinite(got).all())
-    err = float((got - r64).abs().max())
-    e32 = float((r32.double() - r64).abs().max())
-    bound = 4 * max(e32, 2.0 ** -24 * float(r64.abs().max()))
-    _note(loss, case, err / bound if bound else float(err > 0))
-    assert err <= bound, (loss, case, err, e32, bound)
-
-
-def _grad(loss, case, got, fn):
-    """fn(dtype) -> the gradient of the restatement by autograd on the CPU.  Relative L2."""
-    g64, g32 = fn(torch.float64), fn(torch.float32)
-    got = got.detach().cpu().double()
-    assert got.shape == g64.shape and bool(torch.isfinite(got).all())
-    nrm = float(g64.norm())
-    if nrm == 0:
-        assert float(got.abs().max()) == 0
-        return
-    err, e32 = float((got - g64).norm()) / nrm, float((g32.double() - g64).norm()) / nrm
-    bound = 4 * max(e32, 1e-6)
-    _note(loss + " grad", case, err / bound)
-    assert err <= bound, (loss, case, err, e32, bound)
+    RATIOS.write()
 
 
 def _autograd(f, x, *rest):
@@ -87,19 +46,6 @@ def _autograd(f, x, *rest):
         f(xa, *(r.to(dtype) if torch.is_tensor(r) and r.is_floating_point() else r for r in rest)).backward()
         return xa.grad
     return run
-
-
-def _place(t, offset=0):
-    """A contiguous device copy whose pointer is 16-byte aligned (offset 0) or one element past."""
-    buf = torch.empty(t.numel() + offset, dtype=t.dtype, device=_dev())
-    v = buf[offset:].view(t.shape)
-    v.copy_(t)
-    assert (v.data_ptr() % 16 == 0) == (offset == 0)
-    return v.detach()
-
-
-def _bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and bool((a.view(torch.int32) == b.view(torch.int32)).all())
 
 
 # ---- SSIM forward ------------------------------------------------------------------------------
@@ -322,7 +268,7 @@ def test_hierarchy_loss(shape):
                             dx, dt_)
     ref64 = lr.hierarchy(x.double(), t.double())
     e32 = abs(float(lr.hierarchy(x, t)) - float(ref64))
-    bound = 4 * max(e32, 2.0 ** -24 * abs(float(ref64)))
+    bound = MARGIN * max(e32, U32 * abs(float(ref64)))
     assert abs(float(out.detach()) - float(parts)) <= 2 * bound
     g64 = _autograd(lr.hierarchy, x, t)(torch.float64)
     assert float((dxg.grad - pgrad).norm()) / float(g64.norm()) <= 2 * 4e-6

@@ -14,7 +14,6 @@ Every comparison prints its ratio err / bound; THZ_METRICS_PARITY_LOG=<file> wri
 """
 import functools
 import math
-import os
 
 import pytest
 import torch
@@ -22,54 +21,23 @@ import torch
 from quantizationawarethzdoe_amd import optics, qat
 from quantizationawarethzdoe_amd.utils import metrics
 from tests import metrics_ref as mr
+from tests.gpu_util import bits as _bits, dev as _dev, place as _place
+from tests.parity import Ratios
 
 pytestmark = pytest.mark.gpu
 
-RATIOS = {}
+RATIOS = Ratios("THZ_METRICS_PARITY_LOG", "# largest err / bound per quantity; bounds: sums count 2^-52 |fp64|; backward 4 max(e32, 2^-24 "
+                "|value|), maximum norm; crossings 4 2^-53 (|t| + |v0|) / |v1 - v0| + 2^-52 W\n")
+_note = RATIOS.note
 SHAPES = [(1, 1), (37, 53), (64, 256), (130, 1030)]
 DTYPES = {"complex64": torch.complex64, "float32": torch.float32, "complex128": torch.complex128}
 EPS = 2.0 ** -52
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
 @pytest.fixture(scope="module", autouse=True)
 def _ratio_log():
     yield
-    path = os.environ.get("THZ_METRICS_PARITY_LOG")
-    if path:
-        with open(path, "w") as fh:
-            fh.write("# largest err / bound per quantity; bounds: sums count 2^-52 |fp64|; backward 4 max(e32, 2^-24 "
-                     "|value|), maximum norm; crossings 4 2^-53 (|t| + |v0|) / |v1 - v0| + 2^-52 W\n")
-            for k in sorted(RATIOS):
-                fh.write(f"{k:28s} {RATIOS[k][0]:.4f}   ({RATIOS[k][1]})\n")
-
-
-def _note(what, case, ratio):
-    print(f"{what:26s} {case:60s} err / bound = {ratio:.4f}")
-    if what not in RATIOS or ratio > RATIOS[what][0]:
-        RATIOS[what] = (ratio, case)
-
-
-def _bits(a, b):
-    a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    if a.is_complex():
-        a, b = torch.view_as_real(a), torch.view_as_real(b)
-    wide = torch.int64 if a.element_size() == 8 else torch.int32
-    return bool((a.view(wide) == b.view(wide)).all())
-
-
-def _place(t, offset=0):
-    """A contiguous device copy whose pointer is 16-byte aligned (offset 0) or one element past."""
-    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=_dev())
-    v = buf[offset:offset + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert (v.data_ptr() % 16 == 0) == (offset == 0 or t.element_size() == 16)
-    return v.detach()
+    RATIOS.write()
 
 
 # ---- inputs, region tables and their float64 results, each made once ------------------------------

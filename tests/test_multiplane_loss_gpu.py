@@ -20,15 +20,10 @@ from hypothesis import HealthCheck, given, settings
 from hypothesis import strategies as st
 
 from tests.golden_io import rel_l2
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
 C0 = 2.998e8
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda:0")
 
 
 @pytest.mark.parametrize("H,ps,Z,B,shared", [(100, 2, 2, 1, False), (100, 2, 3, 2, True), (100, 4, 5, 1, True),

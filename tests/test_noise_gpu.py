@@ -15,7 +15,6 @@ MI355X (profiles/noise_parity_ratios.txt; every case prints its line, THZ_NOISE_
 appends them to a file).
 """
 import math
-import os
 
 import numpy as np
 import pytest
@@ -27,6 +26,8 @@ from quantizationawarethzdoe_amd.DataType.ElectricField import ElectricField
 from quantizationawarethzdoe_amd.utils import Noise as U
 from tests import noise_ref as nr
 from tests import noise_stats as ns
+from tests.gpu_util import bits as _bits, dev as _dev, place as _place
+from tests.parity import MARGIN, emit
 
 pytestmark = pytest.mark.gpu
 
@@ -35,37 +36,14 @@ SIGMA, AMP, SNR_DB = 0.25, 0.3, 12.0
 N_STAT = 1 << 20
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
 def _state(seed=1234, step=7):
     return torch.tensor([seed, step], dtype=torch.int32, device=_dev())
-
-
-def _place(t, offset):
-    """A contiguous device copy of ``t`` whose pointer is 16-byte aligned (offset 0) or one element
-    past such an address (offset 1)."""
-    buf = torch.empty(t.numel() + offset, dtype=t.dtype, device=_dev())
-    assert buf.data_ptr() % 16 == 0
-    v = buf[offset:].view(t.shape)
-    v.copy_(t)
-    assert v.is_contiguous() and (v.data_ptr() % 16 == 0) == (offset == 0)
-    return v
 
 
 def _inputs(n, offset, seed=0):
     g = torch.Generator().manual_seed(seed + n)
     return _place(torch.randn(n, generator=g), offset), _place(torch.view_as_complex(torch.randn(n, 2, generator=g)),
                                                                offset)
-
-
-def _bits(a, b):
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    if a.is_complex():
-        a, b = torch.view_as_real(a), torch.view_as_real(b)
-    return bool((a.view(torch.int32) == b.view(torch.int32)).all())
 
 
 @pytest.mark.parametrize("offset", [0, 1])
@@ -272,12 +250,8 @@ def test_snr_gradient_against_autograd(cplx):
     floor_t, got_t = _rel(g32 - gout, g64 - gout.to(g64.dtype)), _rel(x.grad - gout, g64 - gout.to(g64.dtype))
     line = (f"snr_gradient {'complex64' if cplx else 'float32'} n={n}: rel-L2 vs fp64 autograd {got:.3e}, torch fp32 "
             f"{floor:.3e}, ratio {got / floor:.3f}; scale term alone {got_t:.3e} / {floor_t:.3e}")
-    print(line)
-    log = os.environ.get("THZ_NOISE_PARITY_LOG")
-    if log:
-        with open(log, "a") as f:
-            f.write(line + "\n")
-    assert got <= 4 * floor, line
+    emit("THZ_NOISE_PARITY_LOG", line)
+    assert got <= MARGIN * floor, line
 
 
 def test_graph_replay_draws_afresh():

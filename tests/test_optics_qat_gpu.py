@@ -8,23 +8,18 @@ propagations, SURVEY.md §8(c) ASM bound 1e-4); the 20-step QAT trace with the r
 draws injected: per-step loss within 1e-3 relative and final weights within 1e-3 rel-L2
 (Adam's normalised step amplifies fp32 differences of near-zero gradients).
 """
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
-from tests.golden_io import arrays, manifest, rel_l2
+from tests.golden_io import arrays, manifest, rel_l2, replay_draws
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
 M = manifest()
 C0 = 2.998e8
 MM = 1e-3
 OPT = M.get("optics", [])
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _ef(x, freqs, dx, dy):
@@ -88,36 +83,6 @@ def test_intensity_mse_large_batch_vs_oracle():
     (ld * 3.0).backward()
     assert abs(float(ld.detach()) - float(lo.detach())) <= 1e-5 * float(lo.detach())
     assert rel_l2(xd.grad.cpu().numpy(), xo.grad.numpy()) <= 1e-4
-
-
-@contextlib.contextmanager
-def replay_draws(layer, A, steps, kinds):
-    """Feed the recorded exponential_ / rand_like draws of each step to the layer in order."""
-    expo, unif = [], []
-    for s in range(steps):
-        for i, k in enumerate(kinds[s]):
-            (expo if k == "expo" else unif).append(A[f"step{s}__draw{i}"])
-    expo.reverse()
-    unif.reverse()
-    orig = torch.rand_like
-
-    def fake_unif(t, *a, **kw):
-        v = unif.pop()
-        assert tuple(t.shape) == v.shape
-        return torch.from_numpy(v).to(device=t.device, dtype=t.dtype)
-
-    def fake_expo(shape, like):
-        v = expo.pop()
-        assert tuple(shape) == v.shape
-        return torch.from_numpy(v).to(like.device)
-
-    layer._gumbel_noise = fake_expo
-    torch.rand_like = fake_unif
-    try:
-        yield
-    finally:
-        torch.rand_like = orig
-    assert not expo and not unif, "not every recorded draw was consumed"
 
 
 def test_qat_four_focal_spots_trace_vs_golden():

@@ -10,13 +10,9 @@ import copy
 import pytest
 import torch
 
+from tests.gpu_util import dev as _dev
+
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda:0")
 
 
 SIZES = [(50, 50), (1,), (3, 1025), (100, 100), (7,)]

@@ -25,15 +25,13 @@ import numpy as np  # noqa: E402
 import pytest  # noqa: E402
 import torch  # noqa: E402
 
+from tests.gpu_util import dev as _dev
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "polarization_golden.npz")
 U24 = 2.0 ** -24
 EPS = 1e-6
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 @functools.lru_cache(maxsize=None)

@@ -27,6 +27,7 @@ from hypothesis import HealthCheck, assume, example, given, settings
 from hypothesis import strategies as st
 
 from oracle import thz_oracle as orc
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
 C0 = 2.998e8
@@ -35,10 +36,6 @@ C0 = 2.998e8
 SETTINGS = settings(max_examples=int(os.environ.get("THZ_PROP_EXAMPLES", "50")), deadline=None,
                     derandomize=os.environ.get("THZ_PROP_RANDOM", "0") != "1", database=None,
                     suppress_health_check=[HealthCheck.too_slow, HealthCheck.data_too_large])
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _rand(rng, shape, dtype):

@@ -18,14 +18,9 @@ import pytest
 import torch
 
 from tests.golden_io import GOLDEN, rel_l2
+from tests.gpu_util import dev as _dev
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda:0")
 
 
 def _golden(name):

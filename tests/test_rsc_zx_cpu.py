@@ -5,9 +5,12 @@ spectra and one chunk's partial sums only, and the identity the kernels implemen
 one-dimensional convolutions for one output row -- equals the oracle's planes in fp64.
 """
 import ctypes
+import functools
 
 import pytest
 import torch
+
+from tests.gpu_util import workspace_size
 
 # (H, W, C, B, (dx, dy)): the scalar geometries of tests/test_rsc_zx_gpu.py and two tiny ones
 GEOMETRIES = [
@@ -41,11 +44,7 @@ def _forward(d, inp=8, out=8, ws=8, ws_bytes=1 << 40):
     return code, _lib.lib().thz_last_error().decode()
 
 
-def _size(d):
-    from quantizationawarethzdoe_amd import _lib
-    n = ctypes.c_size_t(0)
-    code = _lib.lib().thz_rsc_slice_workspace_size(ctypes.byref(d), ctypes.byref(n))
-    return code, n.value, _lib.lib().thz_last_error().decode()
+_size = functools.partial(workspace_size, "thz_rsc_slice_workspace_size")
 
 
 def test_symbols_exported_and_abi_9():

@@ -8,11 +8,13 @@ row; VRS's third plane inverted per plane for its x/r, y/r factors -- written ou
 autograd equals autograd through the oracle's planes.
 """
 import ctypes
+import functools
 
 import pytest
 import torch
 
 from oracle import thz_oracle as orc
+from tests.gpu_util import workspace_size
 
 
 def _desc(H=1024, W=1024, C=2, B=1, Z=3, row=5, vectorial=0, **kw):
@@ -36,13 +38,7 @@ def _adjoint(d, gout=8, gin=8, ws=8, ws_bytes=1 << 40):
     return code, _lib.lib().thz_last_error().decode()
 
 
-def _size(d, forward=False):
-    from quantizationawarethzdoe_amd import _lib
-    L = _lib.lib()
-    n = ctypes.c_size_t(0)
-    fn = L.thz_rsc_slice_workspace_size if forward else L.thz_rsc_slice_adjoint_workspace_size
-    code = fn(ctypes.byref(d), ctypes.byref(n))
-    return code, n.value, L.thz_last_error().decode()
+_size = functools.partial(workspace_size, "thz_rsc_slice_adjoint_workspace_size")
 
 
 def test_symbols_exported_bound_and_abi_9():
@@ -101,7 +97,7 @@ def test_shape_rules_are_the_forwards():
                      (dict(B=0), _lib.THZ_E_ARG), (dict(H=64, W=8194), _lib.THZ_E_UNSUPPORTED)):
         _, d = _desc(**kw)
         code, msg = _adjoint(d)
-        fcode, _, fmsg = _size(d, forward=True)
+        fcode, _, fmsg = workspace_size("thz_rsc_slice_workspace_size", d)
         assert code == want == _size(d)[0] == fcode, (kw, code, msg)
         assert msg == fmsg, "one validation function: the forward's messages"
     _, d = _desc(vectorial=1, B=2)
@@ -180,7 +176,7 @@ CASES = [
 ]
 
 
-def _lam(C):
+def _synthetic_lam(C):
     return torch.tensor([1e-3 * (1 + 0.1 * c) for c in range(C)])
 
 
@@ -196,7 +192,7 @@ def _three_step_adjoint(g, H, W, C, dx, dy, zs, row, vectorial):
     """grad_in [B, C, H, W] of the cotangent g [Z, Bo, C, Wo], by the three steps of DESIGN.md section 20."""
     Ph, Pw = H + 2 * (H // 2), W + 2 * (W // 2)
     Z, Bo = g.shape[:2]
-    lam = _lam(C)
+    lam = _synthetic_lam(C)
     kw = 2 * torch.pi / lam[:, None, None]
     x = torch.linspace(-Ph * dx / 2, Ph * dx / 2, Ph)
     y = torch.linspace(-Pw * dx / 2, Pw * dx / 2, Pw)
@@ -241,7 +237,7 @@ def test_three_step_adjoint_equals_autograd_through_the_oracle(case):
             if vectorial:
                 fx, fy = _ez_factors(H, W, dx, z)
                 v = torch.cat([x[0:1], x[1:2], x[0:1] * fx + x[1:2] * fy], 0)
-            planes.append(torch.cat([orc.rsc_forward(v[b:b + 1], _lam(C), [dx, dy], z) for b in range(v.shape[0])], 0))
+            planes.append(torch.cat([orc.rsc_forward(v[b:b + 1], _synthetic_lam(C), [dx, dy], z) for b in range(v.shape[0])], 0))
         planes = torch.stack(planes)   # [Z, Bo, C, Ho, Wo]
         for row in (0, Ho // 2, Ho - 1):
             g = torch.randn(len(zs), planes.shape[1], C, Wo, dtype=torch.complex128, generator=gen)

@@ -3,7 +3,7 @@ runs the slice kernels forward (rsc_slice_rows / rsc_slice_acc / rsc_slice_line)
 backward (thz_rsc_slice_adjoint: rsc_slice_line_adj on the cotangent lines, rsc_slice_acc_adj summing
 the planes in the spectrum, rsc_slice_rows_adj), so a loss on the axial map never forms a plane.
 
-Geometries, sweep, ``_lam`` and ``_f32`` are those of tests/test_rsc_zx_gpu.py; inputs and cotangents are
+Geometries, sweep, wavelengths and ``f32`` are those of tests/test_rsc_zx_gpu.py; inputs and cotangents are
 seeded white complex noise.
 
 Bounds (all the project's own):
@@ -23,8 +23,9 @@ import pytest
 import torch
 
 from oracle import thz_oracle as orc
-from tests.test_rsc_zx_gpu import (BATCHES, GEOMETRIES, PLANS, VRS, VRS_1200, VRS_4096, VRS_PLAN, ZS, _dev, _f32,
-                                   _field, _id, _input, _lam, _prop, _rows)
+from tests import rsc_zx_cases as zc
+from tests.gpu_util import dev as _dev, f32 as _f32, launches
+from tests.rsc_zx_cases import BATCHES, GEOMETRIES, PLANS, VRS, VRS_1200, VRS_4096, VRS_PLAN, ZS
 
 pytestmark = pytest.mark.gpu
 
@@ -65,8 +66,8 @@ def _oracle_grads(geo, zs, rows, vectorial=False, exact=False):
     old = torch.get_default_dtype()
     torch.set_default_dtype(torch.float64)
     try:
-        x = _input(geo, dt).to(torch.complex128).requires_grad_(True)
-        lam = torch.tensor([r(v) for v in _lam(C)])
+        x = zc.white_input(geo, dt).to(torch.complex128).requires_grad_(True)
+        lam = torch.tensor([r(v) for v in zc.synthetic_lam(C)])
         acc = {p: torch.zeros(B, C, H, W, dtype=torch.complex128) for p in rows}
         for k, z in enumerate(zs):
             z = r(z)
@@ -89,16 +90,10 @@ def _dot(a, b):
     return complex(torch.vdot(a.reshape(-1).to(torch.complex128).cpu(), b.reshape(-1).to(torch.complex128).cpu()))
 
 
-def _launches(fn, name=ACC_ADJ):
+def _acc_adj_launches(fn, name=ACC_ADJ):
     """(result, launches of the accumulate-adjoint kernel) of fn(): whether the native backward ran."""
-    from quantizationawarethzdoe_amd import _lib
-    _lib.timing_enable(True)
-    try:
-        _lib.timing_reset()
-        out = fn()
-        return out, _lib.timing_read(name)[1]
-    finally:
-        _lib.timing_enable(False)
+    out, (n,) = launches(fn, (name,))
+    return out, n
 
 
 def _slice_vjp(geo, zs, row, g, axis="x", vectorial=False):
@@ -106,26 +101,26 @@ def _slice_vjp(geo, zs, row, g, axis="x", vectorial=False):
     scalar B > 1 (which RSC_prop refuses as the reference does) the two raw launches."""
     from quantizationawarethzdoe_amd import propagation as P
     if vectorial or geo[3] == 1:
-        f = _field(geo, grad=True)
+        f = zc.field(geo, grad=True)
 
         def run():
-            out = _prop(vectorial).propagate_zx(f, list(zs), row=row, axis=axis, grad="slice")
+            out = zc.prop(vectorial).propagate_zx(f, list(zs), row=row, axis=axis, grad="slice")
             gx, = torch.autograd.grad(out, f.data, grad_outputs=g)
             return out.detach(), gx
     else:
         assert axis == "x"
-        x = _input(geo).to(_dev())
+        x = zc.white_input(geo).to(_dev())
 
         def run():
-            return (P.rsc_slice_apply(x, _lam(geo[2]), geo[4], list(zs), row),
-                    P.rsc_slice_adjoint(g, _lam(geo[2]), geo[4], list(zs), row, x.shape))
-    (out, gx), n = _launches(run)
+            return (P.rsc_slice_apply(x, zc.synthetic_lam(geo[2]), geo[4], list(zs), row),
+                    P.rsc_slice_adjoint(g, zc.synthetic_lam(geo[2]), geo[4], list(zs), row, x.shape))
+    (out, gx), n = _acc_adj_launches(run)
     return out, gx, n
 
 
 def _planes_vjp(geo, zs, row, g, axis="x", vectorial=False):
-    f = _field(geo, grad=True)
-    (out, gx), n = _launches(lambda: _vjp_of(_prop(vectorial).propagate_zx(f, list(zs), row=row, axis=axis,
+    f = zc.field(geo, grad=True)
+    (out, gx), n = _acc_adj_launches(lambda: _vjp_of(zc.prop(vectorial).propagate_zx(f, list(zs), row=row, axis=axis,
                                                                          grad="planes"), f.data, g))
     assert n == 0, "grad='planes' never runs the slice adjoint"
     return out, gx
@@ -142,10 +137,10 @@ def _full_adjoint(geo, zs, row, g, vectorial=False):
     from quantizationawarethzdoe_amd.propagation import rsc_apply
     from quantizationawarethzdoe_amd.Props.RSC_Prop import _RscFunction
     H, W, C, B = geo[:4]
-    wl, sp = tuple(_lam(C)), tuple(geo[4])
+    wl, sp = tuple(zc.synthetic_lam(C)), tuple(geo[4])
     res = torch.zeros(B, C, H, W, dtype=torch.complex64, device=_dev())
     G = torch.zeros(g.shape[1], C, 2 * (H // 2), 2 * (W // 2), dtype=torch.complex64, device=_dev())
-    x = _input(geo).to(_dev()).requires_grad_(True)
+    x = zc.white_input(geo).to(_dev()).requires_grad_(True)
     for k, z in enumerate(zs):
         G[:, :, row, :] = g[k]
         if vectorial:
@@ -156,9 +151,9 @@ def _full_adjoint(geo, zs, row, g, vectorial=False):
 
 
 def _check_identity(geo, vectorial=False, axis="x"):
-    x = _input(geo).to(_dev())
+    x = zc.white_input(geo).to(_dev())
     n_out = 2 * (geo[0] // 2) if axis == "x" else 2 * (geo[1] // 2)
-    for row in _rows(n_out):
+    for row in zc.rows(n_out):
         g = _cotangent(geo, len(ZS), row, vectorial).to(_dev())
         Ax, AHg, n = _slice_vjp(geo, ZS, row, g, vectorial=vectorial)
         assert n == 1 and AHg.shape == x.shape and AHg.dtype == torch.complex64
@@ -169,7 +164,7 @@ def _check_identity(geo, vectorial=False, axis="x"):
 
 
 def _check_gradient(geo, zs, vectorial=False, oracle=True):
-    rows = _rows(2 * (geo[0] // 2))
+    rows = zc.rows(2 * (geo[0] // 2))
     want = _oracle_grads(geo, tuple(zs), tuple(rows), vectorial)
     for row in rows:
         g = _cotangent(geo, len(zs), row, vectorial).to(_dev())
@@ -184,12 +179,12 @@ def _check_gradient(geo, zs, vectorial=False, oracle=True):
         assert e_pl <= PLANES_TOL, (geo[:4], row, e_pl)
 
 
-@pytest.mark.parametrize("geo", SCALAR + [WIDE], ids=_id)
+@pytest.mark.parametrize("geo", SCALAR + [WIDE], ids=zc.case_id)
 def test_adjoint_identity_against_the_native_forward(geo):
     _check_identity(geo)
 
 
-@pytest.mark.parametrize("geo", SCALAR, ids=_id)
+@pytest.mark.parametrize("geo", SCALAR, ids=zc.case_id)
 def test_gradient_vs_oracle_and_full_plane_adjoint(geo):
     _check_gradient(geo, ZS)
 
@@ -199,7 +194,7 @@ def test_widest_line_vs_full_plane_adjoint():
     _check_gradient(WIDE, ZS, oracle=False)
 
 
-@pytest.mark.parametrize("geo", [VRS, VRS_PLAN, VRS_1200, VRS_4096], ids=_id)
+@pytest.mark.parametrize("geo", [VRS, VRS_PLAN, VRS_1200, VRS_4096], ids=zc.case_id)
 def test_vrs_gradient(geo):
     """The identity, both bounds, and consistency: with a zero third cotangent plane the Ex / Ey
     gradients are bit-equal to the scalar slice adjoint of the same two lines (B = 2, raw launch)."""
@@ -207,11 +202,11 @@ def test_vrs_gradient(geo):
     H, W, C = geo[:3]
     _check_identity(geo, vectorial=True)
     _check_gradient(geo, ZS, vectorial=True)
-    for row in _rows(2 * (H // 2)):
+    for row in zc.rows(2 * (H // 2)):
         g = _cotangent(geo, len(ZS), row, True).to(_dev()).clone()
         g[:, 2] = 0
-        vec = P.rsc_slice_adjoint(g, _lam(C), geo[4], list(ZS), row, (2, C, H, W), vectorial=True)
-        sca = P.rsc_slice_adjoint(g[:, :2].contiguous(), _lam(C), geo[4], list(ZS), row, (2, C, H, W))
+        vec = P.rsc_slice_adjoint(g, zc.synthetic_lam(C), geo[4], list(ZS), row, (2, C, H, W), vectorial=True)
+        sca = P.rsc_slice_adjoint(g[:, :2].contiguous(), zc.synthetic_lam(C), geo[4], list(ZS), row, (2, C, H, W))
         assert torch.equal(vec, sca), (geo[:4], row)
 
 
@@ -219,12 +214,12 @@ def test_vrs_gradient(geo):
                          ids=["72x100", "20x24", "vrs40x48"])
 def test_public_slice_against_planes(geo, vectorial):
     """Values and gradients of the two ``grad`` forms; the forward alone launches no adjoint kernel."""
-    for row in _rows(2 * (geo[0] // 2)):
+    for row in zc.rows(2 * (geo[0] // 2)):
         g = _cotangent(geo, len(ZS), row, vectorial).to(_dev())
-        f = _field(geo, grad=True)
-        out, n = _launches(lambda: _prop(vectorial).propagate_zx(f, list(ZS), row=row, grad="slice"))
+        f = zc.field(geo, grad=True)
+        out, n = _acc_adj_launches(lambda: zc.prop(vectorial).propagate_zx(f, list(ZS), row=row, grad="slice"))
         assert n == 0 and out.grad_fn is not None
-        _, fwd = _launches(lambda: _prop(vectorial).propagate_zx(f, list(ZS), row=row, grad="slice"), "rsc_slice_acc")
+        _, fwd = _acc_adj_launches(lambda: zc.prop(vectorial).propagate_zx(f, list(ZS), row=row, grad="slice"), "rsc_slice_acc")
         assert fwd == 1, "grad='slice' runs the slice kernels forward on a field that requires grad"
         o1, g1, n = _slice_vjp(geo, ZS, row, g, vectorial=vectorial)
         o2, g2 = _planes_vjp(geo, ZS, row, g, vectorial=vectorial)
@@ -240,7 +235,7 @@ def test_sweep_longer_than_max_z():
     from quantizationawarethzdoe_amd import _lib
     geo, Z = GEOMETRIES[3], _lib.THZ_MAX_Z + 3
     zs = tuple(0.03 + 0.06 * (k / (Z - 1)) ** 1.5 for k in range(Z))
-    rows = _rows(geo[0])
+    rows = zc.rows(geo[0])
     want = _oracle_grads(geo, zs, tuple(rows))
     for row in rows:
         g = _cotangent(geo, Z, row).to(_dev())
@@ -255,7 +250,7 @@ def test_sweep_longer_than_max_z():
 def test_axis_y_against_planes(vectorial):
     geo = VRS if vectorial else GEOMETRIES[0]   # dx != dy: the kernel's grid takes dx on both axes
     H, W, C = geo[:3]
-    for row in _rows(2 * (W // 2)):
+    for row in zc.rows(2 * (W // 2)):
         gen = torch.Generator().manual_seed(17 + row)
         g = torch.randn(len(ZS), 3 if vectorial else 1, C, 2 * (H // 2), dtype=torch.complex64, generator=gen).to(_dev())
         o1, g1, n = _slice_vjp(geo, ZS, row, g, axis="y", vectorial=vectorial)
@@ -275,15 +270,15 @@ def test_out_buffer_is_overwritten(Z):
     for geo, vec in ((GEOMETRIES[0], False), (VRS, True)):
         H, W, C, B = geo[:4]
         g = _cotangent(geo, Z, 3, vec).to(_dev())
-        fresh = P.rsc_slice_adjoint(g, _lam(C), geo[4], zs, 3, (B, C, H, W), vec)
+        fresh = P.rsc_slice_adjoint(g, zc.synthetic_lam(C), geo[4], zs, 3, (B, C, H, W), vec)
         buf = torch.full((B, C, H, W), float("nan"), dtype=torch.complex64, device=_dev())
-        got = P.rsc_slice_adjoint(g, _lam(C), geo[4], zs, 3, (B, C, H, W), vec, out=buf)
+        got = P.rsc_slice_adjoint(g, zc.synthetic_lam(C), geo[4], zs, 3, (B, C, H, W), vec, out=buf)
         assert got is buf and torch.isfinite(torch.view_as_real(buf)).all()
         assert torch.equal(torch.view_as_real(buf), torch.view_as_real(fresh))
         with pytest.raises(ValueError, match="out must be"):
-            P.rsc_slice_adjoint(g, _lam(C), geo[4], zs, 3, (B, C, H, W), vec, out=buf[..., :-1])
+            P.rsc_slice_adjoint(g, zc.synthetic_lam(C), geo[4], zs, 3, (B, C, H, W), vec, out=buf[..., :-1])
         with pytest.raises(ValueError, match="gradient"):
-            P.rsc_slice_adjoint(g[:-1], _lam(C), geo[4], zs, 3, (B, C, H, W), vec)
+            P.rsc_slice_adjoint(g[:-1], zc.synthetic_lam(C), geo[4], zs, 3, (B, C, H, W), vec)
 
 
 def test_two_backward_calls_are_bit_identical():
@@ -296,20 +291,20 @@ def test_two_backward_calls_are_bit_identical():
 
 def test_field_without_grad_takes_the_slice_kernels():
     geo, row = GEOMETRIES[0], 7
-    f = _field(geo)
-    got, n = _launches(lambda: _prop().propagate_zx(f, list(ZS), row=row, grad="slice"), "rsc_slice_acc")
+    f = zc.field(geo)
+    got, n = _acc_adj_launches(lambda: zc.prop().propagate_zx(f, list(ZS), row=row, grad="slice"), "rsc_slice_acc")
     assert n == 1 and got.grad_fn is None and not got.requires_grad
-    assert torch.equal(torch.view_as_real(got), torch.view_as_real(_prop().propagate_zx(f, list(ZS), row=row)))
+    assert torch.equal(torch.view_as_real(got), torch.view_as_real(zc.prop().propagate_zx(f, list(ZS), row=row)))
 
 
 def test_complex128_takes_the_fp64_planes():
     geo = GEOMETRIES[3]
-    rows = _rows(geo[0])
+    rows = zc.rows(geo[0])
     want = _oracle_grads(geo, ZS, tuple(rows), False, True)
     for row in rows:
-        f = _field(geo, torch.complex128, grad=True)
+        f = zc.field(geo, torch.complex128, grad=True)
         g = _cotangent(geo, len(ZS), row, False, torch.complex128).to(_dev())
-        (out, gx), n = _launches(lambda: _vjp_of(_prop().propagate_zx(f, list(ZS), row=row, grad="slice"), f.data, g))
+        (out, gx), n = _acc_adj_launches(lambda: _vjp_of(zc.prop().propagate_zx(f, list(ZS), row=row, grad="slice"), f.data, g))
         assert n == 0 and out.dtype == gx.dtype == torch.complex128
         err = _rel(gx, want[row])
         print(f"rsc zx grad complex128 row {row}: vs oracle {err:.3e}")
@@ -321,14 +316,14 @@ def test_gradient_reaches_a_phase_parameter():
     from quantizationawarethzdoe_amd.DataType.ElectricField import ElectricField
     geo = GEOMETRIES[0]
     H, W, C = geo[:3]
-    amp = _input(geo).abs().to(_dev())
-    phi0 = _input(geo).angle().to(_dev())
+    amp = zc.white_input(geo).abs().to(_dev())
+    phi0 = zc.white_input(geo).angle().to(_dev())
     grads = {}
     for form in ("slice", "planes"):
         phi = phi0.clone().requires_grad_(True)
         data = (amp * torch.exp(1j * phi)).to(torch.complex64)
-        f = ElectricField(data, wavelengths=_lam(C), spacing=list(geo[4]), device=_dev())
-        loss, n = _launches(lambda: _backward_of(_prop().propagate_zx(f, list(ZS), row=H // 2, grad=form)))
+        f = ElectricField(data, wavelengths=zc.synthetic_lam(C), spacing=list(geo[4]), device=_dev())
+        loss, n = _acc_adj_launches(lambda: _backward_of(zc.prop().propagate_zx(f, list(ZS), row=H // 2, grad=form)))
         assert n == (1 if form == "slice" else 0)
         grads[form] = phi.grad.detach().clone()
     err = float((grads["slice"] - grads["planes"]).norm() / grads["planes"].norm())

@@ -8,13 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_util import dev as _dev
+
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda:0")
 
 
 def test_step_fetch_replays_read_their_own_slots():

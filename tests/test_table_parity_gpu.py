@@ -14,7 +14,8 @@ element of a large plane cannot hide in.
 
 Bound, on both: err <= MARGIN x floor32(case), floor32 being the identical algebra in complex64 with
 torch's CPU FFT on the same table and input against the complex128 result (measured 1.5e-7 ... 3.7e-7
-rel-L2, 0.26e-6 ... 1.4e-6 max/rms).  MARGIN = 4 allows a different but equally valid fp32 FFT (radix-16 / 8 /
+rel-L2, 0.26e-6 ... 1.4e-6 max/rms).  The rule -- metrics, floor, margin and the judge every family shares -- lives in
+tests/parity.py; MARGIN = 4 allows a different but equally valid fp32 FFT (radix-16 / 8 /
 5 / 4 / 3 / 2 Stockham stages with table twiddles against pocketfft's factorisation, explicit-fmaf
 complex products, split partial sums in the slice kernels): error constants of fp32 FFT variants
 differ by small factors, never by an order of magnitude.  The measured ratios are recorded in
@@ -33,48 +34,18 @@ and tests/test_asm_recurrence_gpu.py owns their 2e-5 bound.  The CZT forms its c
 exports no table: tests/test_czt_parity_gpu.py holds it to the same margin against tests/czt_ref.py.
 """
 import functools
-import os
 
 import pytest
 import torch
 
 from oracle import thz_oracle as orc
+from tests import rsc_zx_cases as zx
 from tests import table_ref as tr
-from tests import test_rsc_zx_gpu as zx
+from tests.gpu_util import C64, dev as _dev, f32 as _f32, launches as _launches, white_cpu as _white
+from tests.parity import MARGIN
+from tests.table_cases import PLANE_KERNELS, AsmCase as _Asm, judge as _judge
 
 pytestmark = pytest.mark.gpu
-
-MARGIN = 4.0
-C0 = 2.998e8
-DX = 0.4e-3
-GHZ = (300, 340)
-C64 = torch.complex64
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _f32(v):
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
-def _white(shape, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, dtype=torch.complex128, generator=g).to(C64)
-
-
-def _launches(fn, names):
-    """(result of fn(), launches of each timed kernel family of ``names``)"""
-    from quantizationawarethzdoe_amd import _lib
-    _lib.timing_enable(True)
-    try:
-        _lib.timing_reset()
-        out = fn()
-        return out, tuple(_lib.timing_read(n)[1] for n in names)
-    finally:
-        _lib.timing_enable(False)
-
 
 # The one family with a margin of its own: runtime plans whose largest prime factor R exceeds 256 run
 # that factor as a generic DFT stage (csrc/thz_fft.hpp stage_generic), every output a sequential fp32
@@ -101,20 +72,6 @@ def _margin(P):
     return TABLE_DFT_MARGIN if _largest_prime_factor(P) > 256 else MARGIN
 
 
-def _judge(family, name, got, ref, floor, MARGIN=MARGIN):
-    """One table-parity line, then the assertion: both metrics within MARGIN of the fp32 floor."""
-    rel, mx = tr.errors(got, ref)
-    line = (f"table-parity {family:<12s} {name:<34s} floor32 {floor[0]:.3e} {floor[1]:.3e}  err {rel:.3e} {mx:.3e}"
-            f"  ratio {rel / floor[0]:5.2f} {mx / floor[1]:5.2f}")
-    print(line)
-    log = os.environ.get("THZ_TABLE_PARITY_LOG")
-    if log:
-        with open(log, "a") as f:
-            f.write(line + "\n")
-    assert rel <= MARGIN * floor[0] and mx <= MARGIN * floor[1], line
-    return rel / floor[0], mx / floor[1]
-
-
 def _judge_planes(family, name, got, ref, lo):
     """[Z, ...] results plane by plane: ``lo`` is the complex64 run of the algebra that gave ``ref``"""
     for k in range(ref.shape[0]):
@@ -124,52 +81,6 @@ def _judge_planes(family, name, got, ref, lo):
 # ---------------------------------------------------------------------------------------------
 # ASM
 # ---------------------------------------------------------------------------------------------
-PLANE_KERNELS = ("asm_rows_fwd", "asm_cols", "asm_rows_inv")
-
-
-class _Asm:
-    """One ASM geometry: the device field, the propagator and the exported tables on the CPU."""
-
-    def __init__(self, H, W, s=1, bl="exact", B=1, C=1, z=None, unpad=True, pad=True, dx=DX, seed=0):
-        from quantizationawarethzdoe_amd.DataType.ElectricField import ElectricField
-        from quantizationawarethzdoe_amd.Props.ASM_Prop import ASM_prop
-        self.ph, self.pw, self.Ph, self.Pw = orc.asm_padding(H, W, s, pad)
-        self.unpad = unpad or not pad
-        self.bl = bl
-        self.z = min(0.4 * self.Ph * dx, 0.12) if z is None else z
-        self.x = _white((B, C, H, W), 1000 * H + W + seed)
-        wl = [_f32(C0 / (f * 1e9)) for f in GHZ[:C]]
-        self.field = ElectricField(self.x.to(_dev()), wavelengths=wl, spacing=[dx, dx], device=_dev())
-        self.prop = ASM_prop(z_distance=self.z, do_padding=pad, do_unpad_after_pad=unpad,
-                             padding_scale=list(s) if isinstance(s, tuple) else s, bandlimit_kernel=bl is not None,
-                             bandlimit_type=bl or "exact", device=_dev())
-        self.prop.check_Zc = False
-        assert self.prop.compute_padding(H, W, True) == (self.ph, self.pw)
-
-    def table(self, z=None):
-        """create_kernel's table for plane z on the CPU, with the band-limit condition: a band-limited
-        case keeps at least 25 % of its table."""
-        keep = self.prop.z
-        if z is not None:
-            self.prop.z = z
-        try:
-            Hc = self.prop.create_kernel(self.field).cpu()
-        finally:
-            self.prop.z = keep
-        assert tuple(Hc.shape[-2:]) == (self.Ph, self.Pw) and Hc.dtype == C64
-        frac = float((Hc != 0).float().mean())
-        if self.bl is not None:
-            assert frac >= 0.25, f"band-limited table keeps {frac:.3f} of its entries"
-        return Hc
-
-    def code(self):
-        return self.prop._bandlimit_code()
-
-    def args(self):
-        """(wavelengths, spacing) as every launch of this field receives them"""
-        return self.field.wavelengths_host, self.field.spacing_host
-
-
 def _asm_forward_case(family, name, P_axis, P, **kw):
     """One plane through ASM_prop.forward against asm_from_table; the padded length of the axis under
     test is the plan the case is meant for, and the planes' three kernels served it once each."""
@@ -357,8 +268,8 @@ def _rsc(geo, zs, vectorial=False):
     from quantizationawarethzdoe_amd.DataType.ElectricField import ElectricField
     from quantizationawarethzdoe_amd.Props.RSC_Prop import RSC_prop
     H, W, C, B, spacing = geo
-    x = zx._input(geo)
-    field = ElectricField(x.to(_dev()), wavelengths=zx._lam(C), spacing=list(spacing), device=_dev())
+    x = zx.white_input(geo)
+    field = ElectricField(x.to(_dev()), wavelengths=zx.synthetic_lam(C), spacing=list(spacing), device=_dev())
     dx, dy = field.spacing_host
     Ks, ref, lo = [], [], []
     for z in zs:
@@ -376,7 +287,7 @@ def _rsc(geo, zs, vectorial=False):
     return field, Ks, torch.stack(ref), torch.stack(lo)
 
 
-@pytest.mark.parametrize("geo", RSC_FIELDS, ids=zx._id)
+@pytest.mark.parametrize("geo", RSC_FIELDS, ids=zx.case_id)
 def test_rsc_forward_and_adjoint(geo):
     from quantizationawarethzdoe_amd import propagation as Pr
     H, W, C, B, _ = geo
@@ -406,7 +317,7 @@ def test_vrs_three_planes():
 SLICES = [(g, False) for g in zx.GEOMETRIES + zx.PLANS + zx.BATCHES] + [(zx.VRS, True), (zx.VRS_4096, True)]
 
 
-@pytest.mark.parametrize("geo, vec", SLICES, ids=[zx._id(g) + ("_vrs" if v else "") for g, v in SLICES])
+@pytest.mark.parametrize("geo, vec", SLICES, ids=[zx.case_id(g) + ("_vrs" if v else "") for g, v in SLICES])
 def test_rsc_slice_forward_and_adjoint(geo, vec):
     """rsc_slice_apply / rsc_slice_adjoint on the zx file's geometries and its non-uniform ZS, rows 0,
     n // 2, n - 1, against the fp64 planes from each plane's own exported table."""

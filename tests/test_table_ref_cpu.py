@@ -102,19 +102,19 @@ def test_rsc_from_table_is_the_oracle(case):
 
 def test_vrs_from_table_is_the_zx_oracle():
     """Ez as tests/test_rsc_zx_gpu._oracle_planes forms it: that file's VRS geometry and sweep."""
-    from tests import test_rsc_zx_gpu as zx
+    from tests import rsc_zx_cases as zx
     geo = zx.VRS
     H, W, C, B, sp = geo
-    want = zx._oracle_planes(geo, zx.ZS, True)
-    dx, dy = zx._f32(sp[0]), zx._f32(sp[1])
-    lam = torch.tensor([zx._f32(v) for v in zx._lam(C)], dtype=torch.float64)
-    x = zx._input(geo)
+    want = zx.oracle_planes(geo, zx.ZS, True)
+    dx, dy = zx.f32(sp[0]), zx.f32(sp[1])
+    lam = torch.tensor([zx.f32(v) for v in zx.synthetic_lam(C)], dtype=torch.float64)
+    x = zx.white_input(geo)
     for k, z in enumerate(zx.ZS):
-        z = zx._f32(z)
+        z = zx.f32(z)
         got = tr.vrs_from_table(x, _rs_table64(H, W, lam, dx, z), dx, dy, z)
         assert got.shape == want[k].shape and _rel(got, want[k]) <= TOL
     # the VRS adjoint against autograd through the forward just pinned
-    z, K = zx._f32(zx.ZS[0]), _rs_table64(H, W, lam, dx, zx._f32(zx.ZS[0]))
+    z, K = zx.f32(zx.ZS[0]), _rs_table64(H, W, lam, dx, zx.f32(zx.ZS[0]))
     xg = x.to(torch.complex128).requires_grad_(True)
     y = tr.vrs_from_table(xg, K, dx, dy, z)
     g = _white(tuple(y.shape), 12)

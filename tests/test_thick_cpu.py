@@ -4,6 +4,7 @@ thz_thick_forward (ABI 9, additive): the symbols are exported and every validati
 code and leaves a message in thz_last_error() before any device call.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -12,6 +13,7 @@ import torch
 from oracle import thz_oracle as orc
 from tests import table_ref as tr
 from tests import thick_ref as th
+from tests.gpu_util import workspace_size
 
 C0 = 2.998e8
 EPS, TAND = 2.66, 0.03
@@ -130,11 +132,7 @@ def _forward(d, field=8, height=8, out=8, ws=8, ws_bytes=1 << 40):
     return code, _lib.lib().thz_last_error().decode()
 
 
-def _size(d):
-    from quantizationawarethzdoe_amd import _lib
-    n = ctypes.c_size_t(0)
-    code = _lib.lib().thz_thick_workspace_size(ctypes.byref(d), ctypes.byref(n))
-    return code, n.value, _lib.lib().thz_last_error().decode()
+_size = functools.partial(workspace_size, "thz_thick_workspace_size")
 
 
 def test_symbols_exported_and_abi_9():

@@ -13,19 +13,18 @@ boundary_heights) in its first entries.  Pixels are one wavelength wide (1 mm at
 T = 4 mm: the regime the model is for.  A case's CPU results are formed once and shared.
 """
 import functools
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from tests import parity
 from tests import table_ref as tr
 from tests import thick_ref as th
+from tests.gpu_util import C0, dev as _dev, launches as _launches, white_cpu as _white
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 4.0
-C0 = 2.998e8
 DX = 1e-3
 EPS, TAND = 2.66, 0.03
 T = 4e-3
@@ -34,36 +33,7 @@ C64 = torch.complex64
 SIGN = {"reference": -1.0, "physical": 1.0}
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _white(shape, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, dtype=torch.complex128, generator=g).to(C64)
-
-
-def _launches(fn, names):
-    from quantizationawarethzdoe_amd import _lib
-    _lib.timing_enable(True)
-    try:
-        _lib.timing_reset()
-        out = fn()
-        return out, tuple(_lib.timing_read(n)[1] for n in names)
-    finally:
-        _lib.timing_enable(False)
-
-
-def _judge(family, name, got, ref, floor):
-    rel, mx = tr.errors(got, ref)
-    line = (f"thick-parity {family:<14s} {name:<40s} floor32 {floor[0]:.3e} {floor[1]:.3e}  err {rel:.3e} {mx:.3e}"
-            f"  ratio {rel / floor[0]:5.2f} {mx / floor[1]:5.2f}")
-    print(line)
-    log = os.environ.get("THZ_THICK_PARITY_LOG")
-    if log:
-        with open(log, "a") as f:
-            f.write(line + "\n")
-    assert rel <= MARGIN * floor[0] and mx <= MARGIN * floor[1], line
+_judge = functools.partial(parity.judge, "THZ_THICK_PARITY_LOG", "thick-parity", widths=(14, 40))
 
 
 class _Case:

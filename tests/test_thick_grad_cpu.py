@@ -5,6 +5,7 @@ thz_thick_backward_workspace_size / thz_thick_backward (ABI 9, additive): export
 path returns its code before any device call.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -13,6 +14,7 @@ import torch
 from oracle import thz_oracle as orc
 from tests import thick_grad_ref as tg
 from tests import thick_ref as th
+from tests.gpu_util import workspace_size
 
 C0 = 2.998e8
 EPS, TAND = 2.66, 0.03
@@ -143,11 +145,7 @@ def _backward(d, gout=8, height=8, stash=8, gfield=8, gheight=8, ws=8, ws_bytes=
     return code, _lib.lib().thz_last_error().decode()
 
 
-def _size(d, name="thz_thick_backward_workspace_size"):
-    from quantizationawarethzdoe_amd import _lib
-    n = ctypes.c_size_t(0)
-    code = getattr(_lib.lib(), name)(ctypes.byref(d), ctypes.byref(n))
-    return code, n.value, _lib.lib().thz_last_error().decode()
+_size = functools.partial(workspace_size, "thz_thick_backward_workspace_size")
 
 
 NEW = ("thz_thick_forward_saved", "thz_thick_backward_workspace_size", "thz_thick_backward")
@@ -223,7 +221,7 @@ def test_backward_workspace_is_the_forwards_and_the_partials(shape):
     _lib, d = _desc(C=C, B=B, H=H, W=W, pad_h=ph, pad_w=pw, hs=H, ws=W)
     code, n, msg = _size(d)
     assert code == _lib.THZ_OK, msg
-    fwd = _size(d, "thz_thick_workspace_size")[1]
+    fwd = workspace_size("thz_thick_workspace_size", d)[1]
     r256 = lambda v: (v + 255) // 256 * 256
     assert n == fwd + r256(4 * B * C * H * W), (shape, n)
     d.slices = 256

@@ -17,7 +17,6 @@ Row-pass code paths (the host dispatch of thz_thick.hip): padded widths 64 .. 51
 case (Pw = 64) are on the first; [1, 1, 32, 512] (Pw = 1024, the smallest such) and the 1024^2 case on the second.
 """
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -26,11 +25,11 @@ import torch
 from tests import table_ref as tr
 from tests import thick_grad_ref as tg
 from tests import thick_ref as th
+from tests.gpu_util import C0, dev as _dev, launches as _launches, white_cpu as _white
+from tests.parity import MARGIN, emit
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 4.0
-C0 = 2.998e8
 DX = 1e-3
 EPS, TAND = 2.66, 0.03
 T = 4e-3
@@ -40,32 +39,7 @@ SIGN = {"reference": -1.0, "physical": 1.0}
 ROWS, COLS, REDUCE = "thick_grad_rows", "thick_grad_cols", "thick_grad_reduce"
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _white(shape, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, dtype=torch.complex128, generator=g).to(C64)
-
-
-def _launches(fn, names):
-    from quantizationawarethzdoe_amd import _lib
-    _lib.timing_enable(True)
-    try:
-        _lib.timing_reset()
-        out = fn()
-        return out, tuple(_lib.timing_read(n)[1] for n in names)
-    finally:
-        _lib.timing_enable(False)
-
-
-def _log(line):
-    print(line)
-    log = os.environ.get("THZ_THICK_GRAD_PARITY_LOG")
-    if log:
-        with open(log, "a") as f:
-            f.write(line + "\n")
+_log = functools.partial(emit, "THZ_THICK_GRAD_PARITY_LOG")
 
 
 class _Case:

@@ -9,26 +9,22 @@ relative L2 and on max|err| / rms.  Every parity case prints its line; THZ_TOLER
 (profiles/tolerance_parity_ratios.txt is such a run on an MI355X).
 """
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from tests import tolerance_ref as tr
+from tests.gpu_util import bits as _bits, dev as _dev, white_cpu as _white
+from tests.parity import MARGIN, emit, errors
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 4.0
 EPS, TAND = 2.66, 0.03
 WL = [float(np.float32(2.998e8 / 300e9)), float(np.float32(2.998e8 / 280e9))]
 LEVELS = (1e-5, 2e-5, 0.0, 4e-5)  # L = 4; level 2 has no error and is not drawn
 ROUGH = {"none": None, "uniform": ("uniform", 5e-6), "normal": ("normal", 3e-6)}
 C64 = torch.complex64
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _mods():
@@ -40,11 +36,6 @@ def _state(seed=1234, step=7):
     return torch.tensor([seed, step], dtype=torch.int32, device=_dev())
 
 
-def _white(shape, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, dtype=torch.complex128, generator=g).to(C64)
-
-
 def _map(hs, ws, seed, L=4):
     """A map in [-1e-4, 1.1e-3] (both sides of the clamp (0, 1e-3) bite) and level indices 0 .. L-1 with the last
     pixel's equal to L, outside the table."""
@@ -53,11 +44,6 @@ def _map(hs, ws, seed, L=4):
     idx = torch.randint(0, L, (hs, ws), generator=g, dtype=torch.int32)
     idx[-1, -1] = L
     return h, idx
-
-
-def _bits(a, b):
-    va, vb = (torch.view_as_real(t) if t.is_complex() else t for t in (a, b))
-    return a.shape == b.shape and a.dtype == b.dtype and bool(va.eq(vb).all())
 
 
 def _draws(optics, state, stream, first, K, hs, ws, rough):
@@ -196,26 +182,12 @@ def test_statistics():
     assert not tr.stat_failures(checks)
 
 
-def _err(got, ref):
-    d = (got.double() if not got.is_complex() else got.to(torch.complex128)) - ref
-    return float(d.abs().pow(2).sum().sqrt() / ref.abs().pow(2).sum().sqrt()), \
-        float(d.abs().max() / ref.abs().pow(2).mean().sqrt())
-
-
-def _log(line):
-    print(line)
-    log = os.environ.get("THZ_TOLERANCE_PARITY_LOG")
-    if log:
-        with open(log, "a") as f:
-            f.write(line + "\n")
-
-
 def _hold(name, got, floor, ref):
     """got and floor against ref on both measures, each at most MARGIN times the floor's."""
-    (gl2, gmx), (fl2, fmx) = _err(got, ref), _err(floor, ref)
+    (gl2, gmx), (fl2, fmx) = errors(got, ref), errors(floor, ref)
     line = (f"{name:28s} relL2 {gl2:.3e} floor {fl2:.3e} ratio {gl2 / fl2:.3f} | max/rms {gmx:.3e} floor {fmx:.3e} "
             f"ratio {gmx / fmx:.3f}")
-    _log(line)
+    emit("THZ_TOLERANCE_PARITY_LOG", line)
     assert gl2 <= MARGIN * fl2 and gmx <= MARGIN * fmx, line
     return fl2
 

@@ -18,6 +18,7 @@ Plain helper module: no test, no fixture, torch and numpy only.
 import numpy as np
 import torch
 
+from tests import parity
 from tests import table_ref as tr
 
 C128 = torch.complex128
@@ -94,10 +95,7 @@ def floor_of(lo, ref, slices):
     on: no better than one fp32 rounding, and per slab no worse than an fp32 FFT pipeline (2e-6 / 2e-5,
     tests/table_ref.floor_of) plus a screen whose phase argument k (d + b)(sqrt(eps) - 1) of up to 20 rad
     rounds by about 1e-6 rad -- twice table_ref's caps per slab."""
-    rel, mx = tr.errors(lo, ref)
-    assert 2.0 ** -24 <= rel <= 4e-6 * slices and rel <= mx <= 4e-5 * slices, \
-        f"floor32 {rel:.3e} {mx:.3e} is not an fp32 pipeline's error over {slices} slabs"
-    return rel, mx
+    return parity.floor_of(lo, ref, rel_cap=4e-6 * slices, max_cap=4e-5 * slices)
 
 
 def boundary_heights(hs, ws, thickness, slices, seed=0):
