@@ -1301,6 +1301,67 @@ typedef struct thz_adam_desc {
 int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stream_t stream);
 
 /*
+ * Hankel propagator for rotationally symmetric fields (not part of the reference; csrc/thz_hankel.hip,
+ * DESIGN 37): the quasi-discrete Hankel transform of Guizar-Sicairos & Gutierrez-Vega (2004).
+ *
+ * For N rings and aperture radius r_max:
+ * - j_1 < ... < j_{N+1} are the first N+1 positive zeros of J0, and S = j_{N+1}.
+ * - Nodes: r_n = j_n r_max / S.
+ * - Radial frequencies: kappa_m = j_m / r_max.
+ * - Weights: w_n = 1 / |J1(j_n)|, for n, m = 1 ... N.
+ * - Table: T[m, n] = 2 J0(j_m j_n / S) / (|J1(j_m)| |J1(j_n)| S). It is real and symmetric.
+ *
+ * For a profile f[b, c, n] = E_{b,c}(r_n), wavelength lambda_c, k_c = 2 pi / lambda_c and distance z:
+ *
+ *     F[b,c,m]     = sum_n T[m,n] w_n f[b,c,n]
+ *     H[z,c,m]     = exp(i z sqrt(k_c^2 - kappa_m^2))   if kappa_m < k_c, else 0      (ASM_prop's evanescent rule and sign)
+ *     out[z,b,c,n] = (1 / w_n) sum_m T[n,m] H[z,c,m] F[b,c,m]                   for n < keep <= N
+ *
+ * The adjoint, which is the backward pass because T is real symmetric and w is real, is:
+ *
+ *     g'[z,b,c,m] = sum_{n<keep} T[m,n] g[z,b,c,n] / w_n
+ *     Fbar[b,c,m] = sum_z conj(H[z,c,m]) g'[z,b,c,m]
+ *     fbar[b,c,n] = w_n sum_m T[n,m] Fbar[b,c,m]
+ *
+ * The field vanishes at r = r_max (the QDHT's boundary): the caller chooses r_max larger than the element, as
+ * padding_scale does for the 2-D propagators.
+ *
+ * T, w and the zeros are formed on the host in extended precision, rounded once (T, w to fp32, the zeros to
+ * fp64) and cached per (N, device); the first call for an N builds them (a host computation and a blocking
+ * copy: not capturable), later calls launch only.  H is formed in fp64, every operation rounded once:
+ * k = 6.283185307179586 / (double)lambda, kappa = j_m / r_max, phase = (double)z * sqrt(k * k - kappa * kappa),
+ * then (cos, sin) of the phase rounded to fp32.  The products run on fp32 MFMA with fixed-order split sums: no
+ * atomics, the same bits from every call.  Wherever two calls split K alike -- always for N <= 128, where K is
+ * one range -- Z planes of one call equal Z one-plane calls bit for bit and keep < N gives the first `keep`
+ * entries of keep = N; the number of splits otherwise follows the shape, and such results agree to rounding.
+ *
+ * profile / grad_profile: complex64 device [B, C, N]; out / grad_out: complex64 device [Z, B, C, keep].
+ * Every argument is checked on the host before any device call (THZ_E_ARG: null pointers, N outside
+ * 1 ... 8192, keep outside 1 ... N, Z, B or C < 1, r_max or a wavelength not positive; THZ_E_WORKSPACE: a
+ * workspace smaller than thz_hankel_workspace_size, which serves both directions; THZ_E_UNSUPPORTED:
+ * C > THZ_MAX_WAVELENGTHS, Z > THZ_MAX_Z, Z B C > 2^20).  The workspace is 256-byte aligned.
+ */
+typedef struct thz_hankel_desc {
+  int N, keep;               /* rings; output rings kept (the first `keep` nodes) */
+  int Z, B, C;
+  double r_max;
+  const float* wavelengths;  /* host [C] */
+  const float* z;            /* host [Z] */
+  const float* z_dev;        /* device [Z], NULL = the host z: a captured graph can move the planes */
+} thz_hankel_desc;
+int thz_hankel_workspace_size(const thz_hankel_desc* d, size_t* bytes);
+int thz_hankel_forward(const thz_hankel_desc* d, const void* profile, void* out, void* workspace,
+                       size_t workspace_bytes, thz_stream_t stream);
+int thz_hankel_adjoint(const thz_hankel_desc* d, const void* grad_out, void* grad_profile, void* workspace,
+                       size_t workspace_bytes, thz_stream_t stream);
+/* What the kernels use, for parity on their own table: T float [N, N], w float [N], the zeros double [N + 1]
+ * (the last is S), device arrays; thz_hankel_table_host writes the same values to host arrays without
+ * touching a device.  H complex64 device [Z, C, N] (B and keep are checked, not used). */
+int thz_hankel_table(int N, float* out_T, float* out_w, double* out_zeros, thz_stream_t stream);
+int thz_hankel_table_host(int N, float* out_T, float* out_w, double* out_zeros);
+int thz_hankel_transfer_function(const thz_hankel_desc* d, void* out, thz_stream_t stream);
+
+/*
  * Per-kernel HIP-event timing used by bench.py (not part of the reference): when
  * enabled every kernel launch is bracketed by two events on its own stream;
  * thz_timing_read() synchronises on the pending events and returns the summed
@@ -1316,7 +1377,7 @@ int thz_adam_step(const thz_adam_desc* d, const thz_adam_param* params, thz_stre
  * "ssim_finish", "ssim_bwd"; the height-map entries: "lut_quantize_fwd", "lut_quantize_bwd", "center_difference",
  * "tv_fwd", "tv_finish", "tv_bwd", "center_difference_bwd"; the metrics entries: "region_stats_fwd",
  * "region_stats_finish", "region_stats_bwd", "line_widths"; the tolerance entries: "tolerance_fwd",
- * "tolerance_heights", "tolerance_bwd"; ...).
+ * "tolerance_heights", "tolerance_bwd"; the Hankel entries: "hankel_tf", "hankel_gemm", "hankel_finish"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

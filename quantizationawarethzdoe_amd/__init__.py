@@ -13,7 +13,7 @@ __version__ = "0.6.0"
 _ALIASES = ("DataType", "Props", "Components", "LightSource", "utils", "Addons", "VisTools")
 
 
-_MODULES = ("DataType.ElectricField", "Props.ASM_Prop", "Props.CZT_Prop", "Props.RSC_Prop",
+_MODULES = ("DataType.ElectricField", "Props.ASM_Prop", "Props.CZT_Prop", "Props.RSC_Prop", "Props.Hankel_Prop",
             "Components.QuantizedDOE", "Components.Thin_Lens", "Components.Aperture",
             "Components.quantization", "Components.discrete_doe", "Components.ThickDOE",
             "LightSource.Gaussian_beam", "Addons.Field_Resampler", "Addons.Field_Crop", "Addons.Polarization",
@@ -33,7 +33,7 @@ def install_reference_aliases():
             importlib.import_module(f"{__name__}.{sub}")
         except ModuleNotFoundError:
             pass
-    for own in ("ifta", "tolerance"):  # modules of this port alone
+    for own in ("ifta", "tolerance", "hankel"):  # modules of this port alone
         sys.modules[own] = importlib.import_module(f"{__name__}.{own}")
     for name in _ALIASES:
         mod = importlib.import_module(f"{__name__}.{name}")

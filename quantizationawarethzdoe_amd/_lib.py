@@ -58,6 +58,8 @@ EXPORTED = [
     "thz_fdtd_workspace_size", "thz_fdtd_setup", "thz_fdtd_run", "thz_fdtd_monitors", "thz_fdtd_fields",
     "thz_fdtd_material",
     "thz_tolerance_modulate_forward", "thz_tolerance_modulate_backward",
+    "thz_hankel_workspace_size", "thz_hankel_forward", "thz_hankel_adjoint", "thz_hankel_table",
+    "thz_hankel_table_host", "thz_hankel_transfer_function",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -343,6 +345,18 @@ class ToleranceDesc(ctypes.Structure):
                 ("rng", ctypes.c_void_p), ("stream", ctypes.c_uint)]
 
 
+HANKEL_MAX_N = 8192
+
+
+class HankelDesc(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int), ("keep", ctypes.c_int),
+                ("Z", ctypes.c_int), ("B", ctypes.c_int), ("C", ctypes.c_int),
+                ("r_max", ctypes.c_double),
+                ("wavelengths", ctypes.POINTER(ctypes.c_float)),  # host [C]
+                ("z", ctypes.POINTER(ctypes.c_float)),            # host [Z]
+                ("z_dev", ctypes.c_void_p)]                       # const float* device [Z], NULL = the host z
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -467,6 +481,13 @@ def _declare(lib):
     lib.thz_tolerance_modulate_forward.argtypes = [td, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.thz_tolerance_modulate_backward.argtypes = [td, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                     c_void_p, c_size_t, c_void_p]
+    hd = ctypes.POINTER(HankelDesc)
+    lib.thz_hankel_workspace_size.argtypes = [hd, ctypes.POINTER(c_size_t)]
+    lib.thz_hankel_forward.argtypes = [hd, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_hankel_adjoint.argtypes = [hd, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_hankel_table.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.thz_hankel_table_host.argtypes = [c_int, c_void_p, c_void_p, c_void_p]
+    lib.thz_hankel_transfer_function.argtypes = [hd, c_void_p, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,
