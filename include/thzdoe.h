@@ -1362,6 +1362,57 @@ int thz_hankel_table_host(int N, float* out_T, float* out_w, double* out_zeros);
 int thz_hankel_transfer_function(const thz_hankel_desc* d, void* out, thz_stream_t stream);
 
 /*
+ * Gaussian-mode analysis: Hermite-Gauss decomposition and synthesis (not part of the reference;
+ * csrc/thz_modes.hip).  Purely additive: THZ_ABI_VERSION stays 9, a caller detects the entries
+ * by symbol.
+ *
+ * The normalised mode of order k and waist w along one axis is
+ *
+ *     u_k(x)      = sqrt(sqrt(2) / w) psi_k(sqrt(2) x / w),
+ *     psi_0(t)    = pi^(-1/4) exp(-t^2 / 2),   psi_1 = sqrt(2) t psi_0,
+ *     psi_{k+1}   = sqrt(2 / (k + 1)) t psi_k - sqrt(k / (k + 1)) psi_{k-1},
+ *
+ * so that the integral of u_k u_l over the axis is delta_kl.  Pixel j of n_pix at `pitch` sits at
+ * x_j = (j - (n_pix - 1) / 2) pitch - centre (the coordinates of utils/metrics.py: pixel centres about the
+ * plane's centre pixel, not the linspace of Guassian_beam).  The table G[c, k, j] = u_k(x_j) at waist[c] is
+ * evaluated on the host in long double, rounded once to fp32 and cached per (device, orders, n_pix, pitch,
+ * centre, waists); the first call for a key builds and copies it (blocking: not capturable), later calls launch
+ * only.  With Gy on (M, H, dy, y0, waist_y) and Gx on (N, W, dx, x0, waist_x):
+ *
+ *     thz_hg_analyze     c[b,c,m,n] = scale sum_i sum_j Gy[c,m,i] U[b,c,i,j] Gx[c,n,j]
+ *     thz_hg_synthesize  U[b,c,i,j] = scale sum_m sum_n Gy[c,m,i] c[b,c,m,n] Gx[c,n,j]
+ *
+ * scale = dx dy makes the analysis the overlap integral <u_m u_n, U>; the tables are real, so each entry is the
+ * other's adjoint (the backward pass) at the same scale.  The modes are those of a beam at its waist: a field
+ * with curvature is flattened by the caller first (thz_thin_lens).  Both run on fp32 MFMA; the analysis sums its
+ * row tiles in a fixed ascending order: no atomics, the same bits from every call, and a plane's bits do not
+ * depend on B or C.
+ *
+ * field: complex64 device [B, C, H, W]; coeffs: complex64 device [B, C, M, N].  Every argument is checked on the
+ * host before any device call (THZ_E_ARG: null pointers, an order outside 1 ... 32, B, C, H or W < 1, a pitch or
+ * a waist that is not positive, a centre or scale that is not finite; THZ_E_WORKSPACE: a workspace smaller than
+ * thz_hg_workspace_size; THZ_E_UNSUPPORTED: B C > 65535, H or W > 2^30).  The workspace is 16-byte aligned.
+ */
+typedef struct thz_hg_desc {
+  int B, C, H, W;
+  int M, N;               /* orders along y (rows) and x (columns): mode indices 0 ... M - 1, 0 ... N - 1 */
+  double dx, dy;          /* pitch along columns / rows, metres */
+  double x0, y0;          /* the modes' centre, metres from the centre pixel */
+  const double* waist_x;  /* host [C] */
+  const double* waist_y;  /* host [C] */
+  double scale;
+} thz_hg_desc;
+int thz_hg_workspace_size(const thz_hg_desc* d, size_t* bytes);
+int thz_hg_analyze(const thz_hg_desc* d, const void* field, void* coeffs, void* workspace, size_t workspace_bytes,
+                   thz_stream_t stream);
+int thz_hg_synthesize(const thz_hg_desc* d, const void* coeffs, void* field, thz_stream_t stream);
+/* What the kernels use, for parity on their own table: G float [C, n_modes, n_pix], a device array;
+ * thz_hg_table_host writes the same values to a host array without touching a device. */
+int thz_hg_table(int n_modes, int n_pix, double pitch, double centre, const double* waists, int C, float* out,
+                 thz_stream_t stream);
+int thz_hg_table_host(int n_modes, int n_pix, double pitch, double centre, const double* waists, int C, float* out);
+
+/*
  * Per-kernel HIP-event timing used by bench.py (not part of the reference): when
  * enabled every kernel launch is bracketed by two events on its own stream;
  * thz_timing_read() synchronises on the pending events and returns the summed
@@ -1377,7 +1428,8 @@ int thz_hankel_transfer_function(const thz_hankel_desc* d, void* out, thz_stream
  * "ssim_finish", "ssim_bwd"; the height-map entries: "lut_quantize_fwd", "lut_quantize_bwd", "center_difference",
  * "tv_fwd", "tv_finish", "tv_bwd", "center_difference_bwd"; the metrics entries: "region_stats_fwd",
  * "region_stats_finish", "region_stats_bwd", "line_widths"; the tolerance entries: "tolerance_fwd",
- * "tolerance_heights", "tolerance_bwd"; the Hankel entries: "hankel_tf", "hankel_gemm", "hankel_finish"; ...).
+ * "tolerance_heights", "tolerance_bwd"; the Hankel entries: "hankel_tf", "hankel_gemm", "hankel_finish"; the mode
+ * entries: "hg_analyze", "hg_finish", "hg_synthesize"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

@@ -60,6 +60,7 @@ EXPORTED = [
     "thz_tolerance_modulate_forward", "thz_tolerance_modulate_backward",
     "thz_hankel_workspace_size", "thz_hankel_forward", "thz_hankel_adjoint", "thz_hankel_table",
     "thz_hankel_table_host", "thz_hankel_transfer_function",
+    "thz_hg_workspace_size", "thz_hg_analyze", "thz_hg_synthesize", "thz_hg_table", "thz_hg_table_host",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -357,6 +358,18 @@ class HankelDesc(ctypes.Structure):
                 ("z_dev", ctypes.c_void_p)]                       # const float* device [Z], NULL = the host z
 
 
+HG_MAX_ORDER = 32
+
+
+class HgDesc(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("M", ctypes.c_int), ("N", ctypes.c_int),
+                ("dx", ctypes.c_double), ("dy", ctypes.c_double), ("x0", ctypes.c_double), ("y0", ctypes.c_double),
+                ("waist_x", ctypes.POINTER(ctypes.c_double)),  # host [C]
+                ("waist_y", ctypes.POINTER(ctypes.c_double)),  # host [C]
+                ("scale", ctypes.c_double)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -488,6 +501,12 @@ def _declare(lib):
     lib.thz_hankel_table.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.thz_hankel_table_host.argtypes = [c_int, c_void_p, c_void_p, c_void_p]
     lib.thz_hankel_transfer_function.argtypes = [hd, c_void_p, c_void_p]
+    gd, c_dbl, dptr = ctypes.POINTER(HgDesc), ctypes.c_double, ctypes.POINTER(ctypes.c_double)
+    lib.thz_hg_workspace_size.argtypes = [gd, ctypes.POINTER(c_size_t)]
+    lib.thz_hg_analyze.argtypes = [gd, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_hg_synthesize.argtypes = [gd, c_void_p, c_void_p, c_void_p]
+    lib.thz_hg_table.argtypes = [c_int, c_int, c_dbl, c_dbl, dptr, c_int, c_void_p, c_void_p]
+    lib.thz_hg_table_host.argtypes = [c_int, c_int, c_dbl, c_dbl, dptr, c_int, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,

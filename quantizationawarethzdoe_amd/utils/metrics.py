@@ -16,7 +16,7 @@ import collections
 
 import torch
 
-from .. import optics
+from .. import modes, optics
 
 FocalSweep = collections.namedtuple("FocalSweep", "peak width z_left z_right depth_of_focus")
 
@@ -145,3 +145,32 @@ def focal_sweep(zx, z_list, spacing, level=0.5):
     along_z = optics.line_widths(lw.peak.movedim(0, -1).contiguous(), level)
     zl, zr = _interp(z, along_z.left), _interp(z, along_z.right)
     return FocalSweep(lw.peak, lw.width * float(spacing), zl, zr, zr - zl)
+
+
+def modal_power(field, spacing=None, waist=None, orders=(1, 1), center=(0.0, 0.0)):
+    """The share of each plane's power in every Hermite-Gauss mode, float64 [B, C, M, N]: |c_mn|^2 of
+    ``modes.hg_decompose`` (whose conventions for ``spacing`` = (dx, dy), ``waist`` and ``center`` = (x0, y0) hold
+    here; the field is complex64 [B, C, H, W] or an ElectricField) over the whole-plane power dx dy sum |U|^2 of
+    ``optics.region_stats``.  The shares sum to 1 once M x N modes hold the field.  Differentiable in the field."""
+    x, (dx, dy) = modes.as_field(field, spacing, "modal_power")
+    c = modes.hg_decompose(x, (dx, dy), waist, orders, center)
+    total = optics.region_stats(x, [], "circ").power[..., 0] * (dx * dy)
+    return (c.real.double() ** 2 + c.imag.double() ** 2) / total[..., None, None]
+
+
+def gaussicity(field, spacing=None, waist=None, center=(0.0, 0.0)):
+    """The share of each plane's power that couples into the fundamental Gaussian mode of ``waist`` about
+    ``center``, float64 [B, C]: ``modal_power(...)[..., 0, 0]``."""
+    return modal_power(field, spacing, waist, (1, 1), center)[..., 0, 0]
+
+
+def mode_filter(field, keep_mask, spacing=None, waist=None, center=(0.0, 0.0)):
+    """The field with only some Hermite-Gauss modes kept, complex64 [B, C, H, W]: decompose on the M x N orders of
+    ``keep_mask`` ([M, N], or anything that broadcasts to [B, C, M, N]; bool or real weights, row m the order along
+    y), multiply, synthesise.  Differentiable in the field."""
+    x, sp = modes.as_field(field, spacing, "mode_filter")
+    mask = torch.as_tensor(keep_mask, device=x.device)
+    if mask.dim() < 2:
+        raise ValueError(f"mode_filter: keep_mask is [M, N]; got shape {tuple(mask.shape)}")
+    c = modes.hg_decompose(x, sp, waist, tuple(mask.shape[-2:]), center)
+    return modes.hg_synthesize(c * mask.to(torch.float32), x.shape[-2:], sp, waist, center)
