@@ -1413,6 +1413,67 @@ int thz_hg_table(int n_modes, int n_pix, double pitch, double centre, const doub
 int thz_hg_table_host(int n_modes, int n_pix, double pitch, double centre, const double* waists, int C, float* out);
 
 /*
+ * Time-domain THz pulses: broadband synthesis and per-pixel pulse maps (not part of the reference;
+ * csrc/thz_pulse.hip).  Purely additive: THZ_ABI_VERSION stays 9, a caller detects the entries by
+ * symbol.
+ *
+ * For channel frequencies f_c the caller supplies a complex source spectrum S_c, quadrature weights q_c and time
+ * samples t_j, j < T.  The sign matches ASM_prop's exp(+i z k_z), so the time dependence is exp(-i omega t).
+ *
+ *     Phi[j, c]     = q_c S_c exp(-i 2 pi f_c t_j)                  the table, complex64 [T, C]
+ *     E[b, j, h, w] = sum_c Phi[j, c] U[b, c, h, w]                 the analytic signal, complex64 [B, T, H, W]
+ *
+ * With I_j = |E_j|^2, the per-pixel maps (float32 [B, 5, H, W]) are:
+ *
+ *     W      = sum_j I_j dt_j                                       energy
+ *     peak   = max_j I_j
+ *     t_peak = t_{j*}, j* the smallest j with I_j = peak
+ *     t_mean = sum_j t_j I_j dt_j / W
+ *     t_rms  = sqrt(sum_j (t_j - t_mean)^2 I_j dt_j / W)
+ *
+ * - dt_j are trapezoid weights of the time list, given as a device array [T].
+ * - Time moments are taken about the middle of the time window, so the subtraction is well conditioned.
+ * - A pixel with W = 0 gets t_mean = t_rms = 0 and t_peak = t_0.
+ *
+ * The adjoint of the synthesis, which is its backward because the product is linear, is
+ * Ubar[b, c, p] = sum_j conj(Phi[j, c]) gbar[b, j, p].
+ *
+ * The maps' backward rests on the fact that every differentiable map is a real-weighted sum of I_j.  With
+ * upstream gradients g_W, g_pk, g_tm, g_sigma per pixel:
+ *
+ *     a_j = dt_j [ g_W + g_tm (t_j - t_mean) / W + g_sigma ((t_j - t_mean)^2 - t_rms^2) / (2 t_rms W) ] + g_pk [j = j*]
+ *
+ * - The gradient of L = sum_j a_j I_j in torch's convention (dL/dRe U + i dL/dIm U) is
+ *   Ubar[c] = 2 sum_j conj(Phi[j, c]) a_j E_j, and that is what thz_pulse_maps_backward writes.
+ * - t_peak carries no gradient.
+ * - t_rms = 0 contributes none; W = 0 leaves the terms of g_W and g_pk.
+ * - j* is found again as the sample with t_j = t_peak: the time list is strictly increasing.
+ *
+ * The table is a device array made by the caller (pulse.time_table: f_c = c0 / lambda_c with c0 = 299 792 458 m/s,
+ * the phase 2 pi f_c t_j formed and reduced in fp64, Phi rounded once to fp32), so the exported table is exactly
+ * what the kernels apply.  The products run on fp32 MFMA, W and the moments are fixed-order fp64 sums: no atomics,
+ * no workspace, the same bits from every call, and a batch entry's bits do not depend on B.
+ *
+ * field / grad_field: complex64 device [B, C, H, W]; out / grad_out: complex64 device [B, T, H, W]; table: complex64
+ * device [T, C]; times, dt: float32 device [T]; maps / grad_maps: float32 device [B, 5, H, W] in the order above
+ * (the t_peak plane of grad_maps is not read).  Every argument is checked on the host before any device call
+ * (THZ_E_ARG: a null descriptor or pointer, B, H or W < 1, a complex array not 8-byte aligned or a float array not
+ * 4-byte aligned; THZ_E_UNSUPPORTED: C outside 1 ... THZ_MAX_WAVELENGTHS, T outside 1 ... 4096, H W above 2^31 - 1,
+ * B ceil(H W / 128) above 2^31 - 1).
+ */
+typedef struct thz_pulse_desc {
+  int B, C, T, H, W;
+} thz_pulse_desc;
+int thz_pulse_synthesize(const thz_pulse_desc* d, const void* field, const void* table, void* out, thz_stream_t stream);
+int thz_pulse_adjoint(const thz_pulse_desc* d, const void* grad_out, const void* table, void* grad_field,
+                      thz_stream_t stream);
+int thz_pulse_maps(const thz_pulse_desc* d, const void* field, const void* table, const float* times, const float* dt,
+                   float* maps, thz_stream_t stream);
+int thz_pulse_maps_backward(const thz_pulse_desc* d, const void* field, const void* table, const float* times,
+                            const float* dt, const float* maps, const float* grad_maps, void* grad_field,
+                            thz_stream_t stream);
+
+/*
  * Per-kernel HIP-event timing used by bench.py (not part of the reference): when
  * enabled every kernel launch is bracketed by two events on its own stream;
  * thz_timing_read() synchronises on the pending events and returns the summed
@@ -1429,7 +1490,8 @@ int thz_hg_table_host(int n_modes, int n_pix, double pitch, double centre, const
  * "tv_fwd", "tv_finish", "tv_bwd", "center_difference_bwd"; the metrics entries: "region_stats_fwd",
  * "region_stats_finish", "region_stats_bwd", "line_widths"; the tolerance entries: "tolerance_fwd",
  * "tolerance_heights", "tolerance_bwd"; the Hankel entries: "hankel_tf", "hankel_gemm", "hankel_finish"; the mode
- * entries: "hg_analyze", "hg_finish", "hg_synthesize"; ...).
+ * entries: "hg_analyze", "hg_finish", "hg_synthesize"; the pulse entries: "pulse_synthesize", "pulse_adjoint",
+ * "pulse_maps", "pulse_maps_bwd"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

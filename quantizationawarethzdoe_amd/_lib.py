@@ -61,6 +61,7 @@ EXPORTED = [
     "thz_hankel_workspace_size", "thz_hankel_forward", "thz_hankel_adjoint", "thz_hankel_table",
     "thz_hankel_table_host", "thz_hankel_transfer_function",
     "thz_hg_workspace_size", "thz_hg_analyze", "thz_hg_synthesize", "thz_hg_table", "thz_hg_table_host",
+    "thz_pulse_synthesize", "thz_pulse_adjoint", "thz_pulse_maps", "thz_pulse_maps_backward",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -370,6 +371,14 @@ class HgDesc(ctypes.Structure):
                 ("scale", ctypes.c_double)]
 
 
+PULSE_MAX_T = 4096
+
+
+class PulseDesc(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("C", ctypes.c_int), ("T", ctypes.c_int), ("H", ctypes.c_int),
+                ("W", ctypes.c_int)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -507,6 +516,12 @@ def _declare(lib):
     lib.thz_hg_synthesize.argtypes = [gd, c_void_p, c_void_p, c_void_p]
     lib.thz_hg_table.argtypes = [c_int, c_int, c_dbl, c_dbl, dptr, c_int, c_void_p, c_void_p]
     lib.thz_hg_table_host.argtypes = [c_int, c_int, c_dbl, c_dbl, dptr, c_int, c_void_p]
+    pd = ctypes.POINTER(PulseDesc)
+    lib.thz_pulse_synthesize.argtypes = [pd, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.thz_pulse_adjoint.argtypes = [pd, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.thz_pulse_maps.argtypes = [pd, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.thz_pulse_maps_backward.argtypes = [pd, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,
