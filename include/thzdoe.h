@@ -1474,6 +1474,57 @@ int thz_pulse_maps_backward(const thz_pulse_desc* d, const void* field, const vo
                             thz_stream_t stream);
 
 /*
+ * Direct Rayleigh-Sommerfeld propagation to arbitrary detector points (not part of the reference, which propagates
+ * to grids; csrc/thz_points.hip).  Purely additive: THZ_ABI_VERSION stays 9, a caller detects the entries
+ * by symbol.
+ *
+ * For a field U[b, c, i, j] on the plane z = 0 and points p_m = (x_m, y_m, z_m), z_m > 0:
+ *
+ *     out[b, c, m]        = dx dy sum_{i,j} U[b, c, i, j] G_c(x_m - x_j, y_m - y_i, z_m)
+ *     G_c(X, Y, z)        = exp(i k_c r) z / (2 pi r^2) (1 / r - i k_c),   r = sqrt(X^2 + Y^2 + z^2),  k_c = 2 pi / lambda_c
+ *     grad[b, c, i, j]    = dx dy sum_m conj(G_c(x_m - x_j, y_m - y_i, z_m)) g[b, c, m]              (the adjoint)
+ *
+ * G is the kernel function of RSC_prop and CZT_prop (Props/RSC_Prop.py:159-161).  Pixel centres are
+ * x_j = x0 + (j - (W - 1) / 2) dx and y_i = y0 + (i - (H - 1) / 2) dy: dim -1 is x, dim -2 is y, the grid is centred
+ * on (x0, y0).  The cost is O(M H W) per channel and batch entry; there is no aliasing window, no padding and no
+ * restriction on where the points lie.  No gradient reaches the points.
+ *
+ * Numerical contract:
+ * - Geometry: the points are fp64, and X, Y, r^2 and r are formed in fp64.
+ * - Phase: in turns, t = r (1 / lambda_c) in fp64 with 1 / lambda_c = 1.0 / (double)wavelengths[c], frac(t) in fp64,
+ *   rounded once to fp32; sine and cosine are evaluated on that reduced fp32 argument.
+ * - Amplitude and sums: z / (2 pi r^2) (1 / r, -k_c) dx dy and every accumulation are fp32.
+ * With k r of 1e3 ... 1e5 rad at THz bench distances an fp32 phase would cost 1e-4 ... 1e-2 rad; the fp64 geometry is
+ * formed once per (point, pixel) pair and shared by every channel and batch entry.
+ *
+ * The forward cuts the pixels into `chunks` contiguous ranges so that few points still fill the device, writes the
+ * partial sums [chunks, B, C, M] to the workspace and adds them in ascending order; chunks = 0 takes the library's
+ * choice, a function of the shape alone, and any other value is clamped to 1 ... ceil(H W / 256).  No atomics: a
+ * repeated call gives the same bits, and one batch entry gives the bits it has inside a batch at the same `chunks`.
+ * Nothing blocks: the calls are capturable.
+ *
+ * field / grad_field: complex64 device [B, C, H, W]; points: double device [M, 3]; out / grad_out: complex64 device
+ * [B, C, M].  Every argument is checked on the host before any device call (THZ_E_ARG: a null descriptor or pointer,
+ * B, H, W or M < 1, chunks < 0, a pitch or a wavelength that is not positive, an origin that is not finite, an array
+ * not 8-byte aligned; THZ_E_WORKSPACE: a workspace smaller than thz_rs_points_workspace_size; THZ_E_UNSUPPORTED:
+ * C outside 1 ... THZ_MAX_WAVELENGTHS, H W or B C M above 2^31 - 1, ceil(B / 2) ceil(C / 4) above 65535).  The values
+ * of the points are not read on the host: a point with z <= 0 gives a non-finite or meaningless sum, nothing worse.
+ */
+typedef struct thz_points_desc {
+  int B, C, H, W;
+  int M;                     /* points */
+  int chunks;                /* forward: ranges the pixels are cut into; 0 = the library's choice */
+  double dx, dy;             /* pitch along columns / rows, metres */
+  double x0, y0;             /* the grid's centre, metres */
+  const float* wavelengths;  /* host [C] */
+} thz_points_desc;
+int thz_rs_points_workspace_size(const thz_points_desc* d, size_t* bytes);
+int thz_rs_points_forward(const thz_points_desc* d, const void* field, const double* points, void* out, void* workspace,
+                          size_t workspace_bytes, thz_stream_t stream);
+int thz_rs_points_adjoint(const thz_points_desc* d, const void* grad_out, const double* points, void* grad_field,
+                          thz_stream_t stream);
+
+/*
  * Per-kernel HIP-event timing used by bench.py (not part of the reference): when
  * enabled every kernel launch is bracketed by two events on its own stream;
  * thz_timing_read() synchronises on the pending events and returns the summed
@@ -1491,7 +1542,8 @@ int thz_pulse_maps_backward(const thz_pulse_desc* d, const void* field, const vo
  * "region_stats_finish", "region_stats_bwd", "line_widths"; the tolerance entries: "tolerance_fwd",
  * "tolerance_heights", "tolerance_bwd"; the Hankel entries: "hankel_tf", "hankel_gemm", "hankel_finish"; the mode
  * entries: "hg_analyze", "hg_finish", "hg_synthesize"; the pulse entries: "pulse_synthesize", "pulse_adjoint",
- * "pulse_maps", "pulse_maps_bwd"; ...).
+ * "pulse_maps", "pulse_maps_bwd"; the point-propagation entries: "rs_points_fwd", "rs_points_finish",
+ * "rs_points_adj"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

@@ -14,6 +14,7 @@ _ALIASES = ("DataType", "Props", "Components", "LightSource", "utils", "Addons",
 
 
 _MODULES = ("DataType.ElectricField", "Props.ASM_Prop", "Props.CZT_Prop", "Props.RSC_Prop", "Props.Hankel_Prop",
+            "Props.Points_Prop",
             "Components.QuantizedDOE", "Components.Thin_Lens", "Components.Aperture",
             "Components.quantization", "Components.discrete_doe", "Components.ThickDOE",
             "LightSource.Gaussian_beam", "Addons.Field_Resampler", "Addons.Field_Crop", "Addons.Polarization",
@@ -33,7 +34,7 @@ def install_reference_aliases():
             importlib.import_module(f"{__name__}.{sub}")
         except ModuleNotFoundError:
             pass
-    for own in ("ifta", "tolerance", "hankel", "modes", "pulse"):  # modules of this port alone
+    for own in ("ifta", "tolerance", "hankel", "modes", "pulse", "points"):  # modules of this port alone
         sys.modules[own] = importlib.import_module(f"{__name__}.{own}")
     for name in _ALIASES:
         mod = importlib.import_module(f"{__name__}.{name}")

@@ -62,6 +62,7 @@ EXPORTED = [
     "thz_hankel_table_host", "thz_hankel_transfer_function",
     "thz_hg_workspace_size", "thz_hg_analyze", "thz_hg_synthesize", "thz_hg_table", "thz_hg_table_host",
     "thz_pulse_synthesize", "thz_pulse_adjoint", "thz_pulse_maps", "thz_pulse_maps_backward",
+    "thz_rs_points_workspace_size", "thz_rs_points_forward", "thz_rs_points_adjoint",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -379,6 +380,13 @@ class PulseDesc(ctypes.Structure):
                 ("W", ctypes.c_int)]
 
 
+class PointsDesc(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("M", ctypes.c_int), ("chunks", ctypes.c_int),  # chunks: 0 = the library's choice
+                ("dx", ctypes.c_double), ("dy", ctypes.c_double), ("x0", ctypes.c_double), ("y0", ctypes.c_double),
+                ("wavelengths", ctypes.POINTER(ctypes.c_float))]  # host [C]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -522,6 +530,10 @@ def _declare(lib):
     lib.thz_pulse_maps.argtypes = [pd, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.thz_pulse_maps_backward.argtypes = [pd, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p]
+    qd = ctypes.POINTER(PointsDesc)
+    lib.thz_rs_points_workspace_size.argtypes = [qd, ctypes.POINTER(c_size_t)]
+    lib.thz_rs_points_forward.argtypes = [qd, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_rs_points_adjoint.argtypes = [qd, c_void_p, c_void_p, c_void_p, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,
