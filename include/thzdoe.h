@@ -1525,6 +1525,62 @@ int thz_rs_points_adjoint(const thz_points_desc* d, const void* grad_out, const 
                           thz_stream_t stream);
 
 /*
+ * Zernike wavefront analysis over a circular pupil: projection, Gram matrix, synthesis (not part of the port's
+ * notebooks; the reference parameterises its hologram maps this way; csrc/thz_zernike.hip).  Purely
+ * additive: THZ_ABI_VERSION stays 9, a caller detects the entries by symbol.
+ *
+ * Pupil (x0, y0, R) in metres from the plane's centre pixel.  Pixel (i, j) of an H x W map sits at
+ * x = (j - (W - 1) / 2) dx - x0, y = (i - (H - 1) / 2) dy - y0 (the coordinates of utils/metrics.py); it belongs to the
+ * pupil when x x + y y <= R R, rho = r / R, and every Z_k is 0 outside the pupil.  OSA / ANSI index
+ * k = (n (n + 2) + m) / 2 for 0 <= n <= max_order <= 14, K = (max_order + 1) (max_order + 2) / 2 <= 120.  Orthonormal
+ * on the unit disk:
+ *
+ *     Z = N R_n^|m|(rho) cos(m theta) (m >= 0),  N R_n^|m|(rho) sin(|m| theta) (m < 0),
+ *     N = sqrt(n + 1) (m = 0), sqrt(2 (n + 1)) otherwise,
+ *     R_n^m(rho) = rho^m P_s^(0,m)(t),  s = (n - m) / 2,  t = 2 rho^2 - 1,
+ *     P_0 = 1,  P_1 = ((m + 2) t - m) / 2,  and with c = 2 s + m, D = 2 s (s + m) (c - 2):
+ *     P_s = ((c - 1) c (c - 2) / D t - (c - 1) m^2 / D) P_{s-1} - 2 (s - 1) (s + m - 1) c / D P_{s-2},
+ *     cos((m + 1) theta) = 2 cos(theta) cos(m theta) - cos((m - 1) theta), the same for sin,
+ *
+ * the Jacobi three-term recurrence (the explicit factorial sum cancels in fp32 at n = 14 and is not used).
+ *
+ * Numerical contract:
+ * - fp64, each rounded once to fp32: x, y, r^2 (the pupil test is made on it in fp64), r, rho = r (1 / R),
+ *   t = 2 rho rho - 1, cos(theta) = x (1 / r), sin(theta) = y (1 / r); at r = 0 cos(theta) = 1, sin(theta) = 0.
+ * - fp32 with explicit fused multiply-adds: rho^m by repeated multiplication, the Chebyshev recurrence, the Jacobi
+ *   recurrence carried on q_s = rho^m P_s as u = fma(A, t, -B), q_s = fma(u, q_{s-1}, -(C q_{s-2})), then
+ *   (N q_s) cos(m theta) and (N q_s) sin(m theta).  A, B, C, N are formed in fp64 and rounded once.
+ * - Products: fp32 MFMA; the projection's and the Gram's workgroup partials are summed in ascending order in fp64
+ *   and rounded once.
+ *
+ *     thz_zernike_project      out[b, k]  = sum_p Z_k(p) maps[b, p];   gram[k, k'] = sum_p Z_k(p) Z_k'(p)
+ *     thz_zernike_synthesize   maps[b, p] = sum_k coeffs[b, k] Z_k(p)  (0 outside the pupil)
+ *     thz_zernike_table        out[k, p]  = Z_k(p), what the two generate
+ *
+ * Z is real, so projection and synthesis are each other's adjoint (the backward pass).  thz_zernike_project takes
+ * maps and out (both or neither) and gram (or NULL), at least one of the two; gram is exactly symmetric.  No atomics:
+ * the same bits from every call, and a plane's bits do not depend on B.  Nothing blocks: the calls are capturable.
+ *
+ * maps: float32 device [B, H, W]; out, coeffs: float32 device [B, K]; gram: float32 device [K, K]; table out: float32
+ * device [K, H, W].  Every argument is checked on the host before any device call (THZ_E_ARG: a null descriptor or
+ * pointer, B, H or W < 1, max_order outside 0 ... 14, a pitch or R that is not positive, a centre that is not finite,
+ * an array not 4-byte aligned or a workspace not 16-byte aligned; THZ_E_WORKSPACE: a workspace smaller than
+ * thz_zernike_workspace_size(d, gram != 0); THZ_E_UNSUPPORTED: H W above 2^31 - 1, B above 32 x 65535).
+ */
+typedef struct thz_zernike_desc {
+  int B, H, W;
+  int max_order;   /* n_max: modes 0 ... K - 1 */
+  double dx, dy;   /* pitch along columns / rows, metres */
+  double x0, y0;   /* the pupil's centre, metres from the centre pixel */
+  double R;        /* the pupil's radius, metres */
+} thz_zernike_desc;
+int thz_zernike_workspace_size(const thz_zernike_desc* d, int gram, size_t* bytes);
+int thz_zernike_project(const thz_zernike_desc* d, const float* maps, float* out, float* gram, void* workspace,
+                        size_t workspace_bytes, thz_stream_t stream);
+int thz_zernike_synthesize(const thz_zernike_desc* d, const float* coeffs, float* maps, thz_stream_t stream);
+int thz_zernike_table(const thz_zernike_desc* d, float* out, thz_stream_t stream);
+
+/*
  * Per-kernel HIP-event timing used by bench.py (not part of the reference): when
  * enabled every kernel launch is bracketed by two events on its own stream;
  * thz_timing_read() synchronises on the pending events and returns the summed
@@ -1543,7 +1599,8 @@ int thz_rs_points_adjoint(const thz_points_desc* d, const void* grad_out, const 
  * "tolerance_heights", "tolerance_bwd"; the Hankel entries: "hankel_tf", "hankel_gemm", "hankel_finish"; the mode
  * entries: "hg_analyze", "hg_finish", "hg_synthesize"; the pulse entries: "pulse_synthesize", "pulse_adjoint",
  * "pulse_maps", "pulse_maps_bwd"; the point-propagation entries: "rs_points_fwd", "rs_points_finish",
- * "rs_points_adj"; ...).
+ * "rs_points_adj"; the Zernike entries: "zernike_project", "zernike_finish", "zernike_gram", "zernike_gram_finish",
+ * "zernike_synthesize", "zernike_table"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

@@ -63,6 +63,7 @@ EXPORTED = [
     "thz_hg_workspace_size", "thz_hg_analyze", "thz_hg_synthesize", "thz_hg_table", "thz_hg_table_host",
     "thz_pulse_synthesize", "thz_pulse_adjoint", "thz_pulse_maps", "thz_pulse_maps_backward",
     "thz_rs_points_workspace_size", "thz_rs_points_forward", "thz_rs_points_adjoint",
+    "thz_zernike_workspace_size", "thz_zernike_project", "thz_zernike_synthesize", "thz_zernike_table",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -387,6 +388,15 @@ class PointsDesc(ctypes.Structure):
                 ("wavelengths", ctypes.POINTER(ctypes.c_float))]  # host [C]
 
 
+ZERNIKE_MAX_ORDER = 14
+
+
+class ZernikeDesc(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("max_order", ctypes.c_int),
+                ("dx", ctypes.c_double), ("dy", ctypes.c_double), ("x0", ctypes.c_double), ("y0", ctypes.c_double),
+                ("R", ctypes.c_double)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -534,6 +544,11 @@ def _declare(lib):
     lib.thz_rs_points_workspace_size.argtypes = [qd, ctypes.POINTER(c_size_t)]
     lib.thz_rs_points_forward.argtypes = [qd, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.thz_rs_points_adjoint.argtypes = [qd, c_void_p, c_void_p, c_void_p, c_void_p]
+    zd = ctypes.POINTER(ZernikeDesc)
+    lib.thz_zernike_workspace_size.argtypes = [zd, c_int, ctypes.POINTER(c_size_t)]
+    lib.thz_zernike_project.argtypes = [zd, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_zernike_synthesize.argtypes = [zd, c_void_p, c_void_p, c_void_p]
+    lib.thz_zernike_table.argtypes = [zd, c_void_p, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,

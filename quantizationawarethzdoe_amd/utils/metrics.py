@@ -16,7 +16,7 @@ import collections
 
 import torch
 
-from .. import modes, optics
+from .. import modes, optics, zernike
 
 FocalSweep = collections.namedtuple("FocalSweep", "peak width z_left z_right depth_of_focus")
 
@@ -174,3 +174,14 @@ def mode_filter(field, keep_mask, spacing=None, waist=None, center=(0.0, 0.0)):
         raise ValueError(f"mode_filter: keep_mask is [M, N]; got shape {tuple(mask.shape)}")
     c = modes.hg_decompose(x, sp, waist, tuple(mask.shape[-2:]), center)
     return modes.hg_synthesize(c * mask.to(torch.float32), x.shape[-2:], sp, waist, center)
+
+
+def wavefront_rms(w, spacing, pupil, remove=2):
+    """The rms over the pupil of a float32 map [B, H, W] (or [H, W]) once its Zernike terms up to radial order
+    ``remove`` are taken out (``zernike.residual``; 2 removes piston, tilt, defocus and astigmatism, ``None`` nothing),
+    float64 [B] (or a scalar): the figure a profilometer scan of a relief or an incident beam's aberration is quoted
+    by.  ``pupil`` = (x0, y0, R) in metres from the centre pixel.  No host read; differentiable in ``w``."""
+    res = w if remove is None else zernike.residual(w, spacing, pupil, remove)
+    mask = zernike._mask(zernike._geometry(w.shape, spacing, pupil, 0, "wavefront_rms"), w.device)
+    res = res * mask if remove is None else res
+    return torch.sqrt(res.double().pow(2).sum((-2, -1)) / mask.double().sum())
