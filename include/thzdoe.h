@@ -1581,6 +1581,58 @@ int thz_zernike_synthesize(const thz_zernike_desc* d, const float* coeffs, float
 int thz_zernike_table(const thz_zernike_desc* d, float* out, thz_stream_t stream);
 
 /*
+ * Least-squares 2-D phase unwrapping of a complex field or a wrapped phase map (Ghiglia and Romero; not part of the
+ * reference; csrc/thz_unwrap.hip).  Purely additive: THZ_ABI_VERSION stays 9, a caller detects the entries
+ * by symbol.
+ *
+ * Model, per plane [H, W]:
+ * - Wrapped differences come from the field itself: Dx[i,j] = arg(U[i,j+1] conj U[i,j]), Dy[i,j] = arg(U[i+1,j] conj
+ *   U[i,j]); no angle map is formed and no modulo taken.  For a float32 phase input psi (input = 1) the difference d
+ *   of two pixels becomes d - 2 pi rint(d / 2 pi).
+ * - Edge weights wx[i,j] = min(w[i,j], w[i,j+1]), wy[i,j] = min(w[i,j], w[i+1,j]).  weights = 0: w = 1; 1: the array
+ *   `weights` ([H, W] shared by the planes, wstride = 0, or [BC, H, W], wstride = H W; values in [0, 1]); 2: |U| and
+ *   3: |U|^2, divided by the plane's maximum (formed on the device).  An edge of weight 0 reads neither of its pixels.
+ * - Right-hand side rho[i,j] = wx Dx[i,j] - wx Dx[i,j-1] + wy Dy[i,j] - wy Dy[i-1,j], absent terms 0.
+ * - Direct solve (iters = 0; weights = 0 and both sides powers of two in 64 ... 4096):
+ *   phi = DCT-III_2(DCT-II_2(rho) / lambda), lambda[i,j] = -(s_y[i] + s_x[j]), s[k] = 4 sin^2(pi k / 2N) (a table made
+ *   in double on the host, stored as fp32: a sum of non-negatives, no cancellation near (0, 0)); the (0, 0) coefficient
+ *   is set to 0, so phi has zero mean.
+ * - Weighted solve (iters > 0): preconditioned conjugate gradients on Q phi = rho with the direct solve P^-1 as the
+ *   preconditioner and the weighted Laplacian Q: z = P^-1 r, beta = rz / rz_old, p = z + beta p, alpha = rz / (p.Qp),
+ *   phi += alpha p, r -= alpha Qp, for exactly `iters` steps (nothing syncs).  A step whose rz <= tol^2 rz0, or whose
+ *   rz or p.Qp is not positive and finite, is frozen on the device (alpha = beta = 0).  hist[k, plane] (double)
+ *   = sqrt(rz_k / rz0).  The dot products are fp64 sums of per-workgroup partials in a fixed order.
+ * - Any side that is not a power of two (or is below 64) is embedded in the next one with weight 0 on the padding;
+ *   zero-weight pixels decouple, so the embedded problem is the same least-squares problem.  It needs iters > 0.
+ * - Finish: anchor = 1 shifts phi so that pixel (anchor_row, anchor_col) equals arg U (or psi) there; congruent = 1
+ *   then returns psi + 2 pi rint((phi - psi) / 2 pi) with psi = arg U.
+ * - Residues: q[i,j] = rint((Dx[i,j] + Dy[i,j+1] - Dx[i+1,j] - Dy[i,j]) / 2 pi), int8 [BC, H - 1, W - 1].
+ *
+ * input: complex64 (input = 0) or float32 (input = 1) device [BC, H, W]; out: float32 device [BC, H, W]; hist: double
+ * device [iters, BC] (iters > 0).  No float atomics: the same bits from every call, and a plane's bits do not depend
+ * on BC.  Nothing blocks: the calls are capturable once the per-device tables of a size exist (first call).  Every
+ * argument is checked on the host before any device call (THZ_E_ARG: a null descriptor or pointer, BC < 1, H or W < 2,
+ * an unknown input / weights / anchor kind, amplitude weights of a phase input, iters = 0 where the direct solve does
+ * not apply, an anchor outside the plane, a misaligned array; THZ_E_WORKSPACE: a workspace smaller than
+ * thz_unwrap_workspace_size; THZ_E_UNSUPPORTED: a side above 4096, BC above 65535).
+ */
+typedef struct thz_unwrap_desc {
+  int BC, H, W;
+  int input;               /* 0: complex64 field, 1: float32 wrapped phase */
+  int weights;             /* 0: none, 1: array, 2: amplitude, 3: intensity */
+  int iters;               /* PCG steps; 0: the direct solve */
+  long long wstride;       /* weights = 1: elements between the planes of the array, 0 or H W */
+  double tol;              /* a step with rz <= tol^2 rz0 is frozen */
+  int anchor;              /* 0: none (zero-mean / raw solution), 1: pixel (anchor_row, anchor_col) */
+  int anchor_row, anchor_col;
+  int congruent;
+} thz_unwrap_desc;
+int thz_unwrap_workspace_size(const thz_unwrap_desc* d, size_t* bytes);
+int thz_unwrap_phase(const thz_unwrap_desc* d, const void* input, const float* weights, float* out, double* hist,
+                     void* workspace, size_t workspace_bytes, thz_stream_t stream);
+int thz_unwrap_residues(int BC, int H, int W, int input_kind, const void* input, signed char* out, thz_stream_t stream);
+
+/*
  * Per-kernel HIP-event timing used by bench.py (not part of the reference): when
  * enabled every kernel launch is bracketed by two events on its own stream;
  * thz_timing_read() synchronises on the pending events and returns the summed
@@ -1600,7 +1652,8 @@ int thz_zernike_table(const thz_zernike_desc* d, float* out, thz_stream_t stream
  * entries: "hg_analyze", "hg_finish", "hg_synthesize"; the pulse entries: "pulse_synthesize", "pulse_adjoint",
  * "pulse_maps", "pulse_maps_bwd"; the point-propagation entries: "rs_points_fwd", "rs_points_finish",
  * "rs_points_adj"; the Zernike entries: "zernike_project", "zernike_finish", "zernike_gram", "zernike_gram_finish",
- * "zernike_synthesize", "zernike_table"; ...).
+ * "zernike_synthesize", "zernike_table"; the unwrapping entries: "unwrap_rows_fwd", "unwrap_cols", "unwrap_rows_inv",
+ * "unwrap_direction", "unwrap_scalars", "unwrap_close", "unwrap_residues", "unwrap_wmax", "unwrap_wfill"; ...).
  */
 int thz_timing_enable(int on);
 int thz_timing_reset(void);

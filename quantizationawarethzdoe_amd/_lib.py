@@ -64,6 +64,7 @@ EXPORTED = [
     "thz_pulse_synthesize", "thz_pulse_adjoint", "thz_pulse_maps", "thz_pulse_maps_backward",
     "thz_rs_points_workspace_size", "thz_rs_points_forward", "thz_rs_points_adjoint",
     "thz_zernike_workspace_size", "thz_zernike_project", "thz_zernike_synthesize", "thz_zernike_table",
+    "thz_unwrap_workspace_size", "thz_unwrap_phase", "thz_unwrap_residues",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -397,6 +398,17 @@ class ZernikeDesc(ctypes.Structure):
                 ("R", ctypes.c_double)]
 
 
+UNWRAP_FIELD, UNWRAP_PHASE = 0, 1
+UNWRAP_W_NONE, UNWRAP_W_ARRAY, UNWRAP_W_AMPLITUDE, UNWRAP_W_INTENSITY = range(4)
+
+
+class UnwrapDesc(ctypes.Structure):
+    _fields_ = [("BC", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("input", ctypes.c_int),
+                ("weights", ctypes.c_int), ("iters", ctypes.c_int), ("wstride", ctypes.c_longlong),
+                ("tol", ctypes.c_double), ("anchor", ctypes.c_int), ("anchor_row", ctypes.c_int),
+                ("anchor_col", ctypes.c_int), ("congruent", ctypes.c_int)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -549,6 +561,10 @@ def _declare(lib):
     lib.thz_zernike_project.argtypes = [zd, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.thz_zernike_synthesize.argtypes = [zd, c_void_p, c_void_p, c_void_p]
     lib.thz_zernike_table.argtypes = [zd, c_void_p, c_void_p]
+    ud = ctypes.POINTER(UnwrapDesc)
+    lib.thz_unwrap_workspace_size.argtypes = [ud, ctypes.POINTER(c_size_t)]
+    lib.thz_unwrap_phase.argtypes = [ud, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_unwrap_residues.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,
