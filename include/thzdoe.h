@@ -1633,6 +1633,70 @@ int thz_unwrap_phase(const thz_unwrap_desc* d, const void* input, const float* w
 int thz_unwrap_residues(int BC, int H, int W, int input_kind, const void* input, signed char* out, thz_stream_t stream);
 
 /*
+ * Far-field patterns and diffraction orders: a non-uniform DFT of a plane to arbitrary directions or to a separable
+ * (u, v) grid, and both adjoints (not part of the reference; csrc/thz_farfield.hip).  Purely additive:
+ * THZ_ABI_VERSION stays 9, a caller detects the entries by symbol.
+ *
+ * Field U[b, c, i, j], complex64 [B, C, H, W], of pitch (dx, dy); pixel coordinates are those of utils/metrics.py,
+ *
+ *     x_j = (j - (W - 1) / 2) dx - x0,     y_i = (i - (H - 1) / 2) dy - y0.
+ *
+ * A direction m is a pair d_m = (p_m, q_m) and a per-channel factor s_c (chan_scale, double device [C]) turns it
+ * into cycles per metre: direction cosines (u, v) = (sin theta cos phi, sin theta sin phi) with s_c = 1 / lambda_c, or
+ * spatial frequencies (fx, fy) with s_c = 1.
+ *
+ *     A[b, c, m]    = scale sum_i sum_j U[b, c, i, j] exp(-2 pi i (s_c p_m x_j + s_c q_m y_i))     (forward)
+ *     G[b, c, i, j] = scale sum_m conj(kernel) g[b, c, m]                                           (adjoint)
+ *
+ * scale is dx dy for the angular spectrum and 1 / (H W) for the order amplitudes of a periodic cell.  With
+ * obliquity != 0 (direction cosines only) the forward result is multiplied by -i w_m s_c,
+ * w = sqrt(max(0, 1 - p^2 - q^2)): the Rayleigh-Sommerfeld far-field amplitude r E exp(-i k r) of RSC_prop's kernel
+ * function; the adjoint multiplies g by the conjugate.  The list entries take directions double device [M, 2]; the
+ * grid entries take u double device [Mu] and v double device [Mv], the directions (u[mu], v[mv]), and A is
+ * [B, C, Mv, Mu].
+ *
+ * Numerical contract of a table entry Ex[j, m] = exp(-2 pi i s_c p_m x_j) (Ey alike), that of thz_rs_points per axis:
+ * - the coordinate is fl64(xc + fl64(j dx)) with xc = -0.5 (W - 1) dx - x0, the frequency fl64(s_c p_m);
+ * - the phase in turns t = fl64(coordinate frequency), r = t - rint(t) in fp64, rounded once to fp32;
+ * - cosine and sine of 2 pi r in fp32 (the hardware pair that takes turns);
+ * - products and sums are fp32: MFMA for the table products, plain for the list's second axis and the factors.
+ * The fp64 product is commutative, so the forward and adjoint tables have the same bits.  The obliquity factor is
+ * fl32(fl64(w) s_c).  thz_farfield_table writes one axis' forward table, complex64 device [C, M, n_pix], exactly as
+ * the kernels form it (p is read at p[m stride]).
+ *
+ * No atomics: a repeated call gives the same bits and a plane's bits do not depend on B or C.  The directions and
+ * chan_scale are read on the device only, so nothing blocks and the calls are capturable.  Every argument is checked
+ * on the host before any device call (THZ_E_ARG: a null descriptor or pointer, B, C, H, W < 1, M < 1 (list) or Mu,
+ * Mv < 1 (grid), a pitch that is not positive, a centre or scale that is not finite, an array not 8-byte aligned;
+ * THZ_E_WORKSPACE: a workspace smaller than thz_farfield_workspace_size(d, grid); THZ_E_UNSUPPORTED:
+ * C > THZ_MAX_WAVELENGTHS, B C > 65535, a side or a direction count above 2^24).  thz_farfield_list_adjoint needs no
+ * workspace.
+ */
+typedef struct thz_farfield_desc {
+  int B, C, H, W;
+  int M;           /* list entries: directions */
+  int Mu, Mv;      /* grid entries: lengths of u and v */
+  int obliquity;   /* != 0: the factor -i w s_c */
+  double dx, dy;   /* pitch along columns / rows, metres */
+  double x0, y0;   /* the origin of the pixel coordinates, metres from the centre pixel */
+  double scale;
+} thz_farfield_desc;
+int thz_farfield_workspace_size(const thz_farfield_desc* d, int grid, size_t* bytes);
+int thz_farfield_list_forward(const thz_farfield_desc* d, const void* field, const double* directions,
+                              const double* chan_scale, void* out, void* workspace, size_t workspace_bytes,
+                              thz_stream_t stream);
+int thz_farfield_list_adjoint(const thz_farfield_desc* d, const void* grad_out, const double* directions,
+                              const double* chan_scale, void* grad_field, thz_stream_t stream);
+int thz_farfield_grid_forward(const thz_farfield_desc* d, const void* field, const double* u, const double* v,
+                              const double* chan_scale, void* out, void* workspace, size_t workspace_bytes,
+                              thz_stream_t stream);
+int thz_farfield_grid_adjoint(const thz_farfield_desc* d, const void* grad_out, const double* u, const double* v,
+                              const double* chan_scale, void* grad_field, void* workspace, size_t workspace_bytes,
+                              thz_stream_t stream);
+int thz_farfield_table(int n_pix, double pitch, double centre, const double* p, long long stride, int M,
+                       const double* chan_scale, int C, void* out, thz_stream_t stream);
+
+/*
  * Per-kernel HIP-event timing used by bench.py (not part of the reference): when
  * enabled every kernel launch is bracketed by two events on its own stream;
  * thz_timing_read() synchronises on the pending events and returns the summed

@@ -34,7 +34,7 @@ def install_reference_aliases():
             importlib.import_module(f"{__name__}.{sub}")
         except ModuleNotFoundError:
             pass
-    for own in ("ifta", "tolerance", "hankel", "modes", "pulse", "points", "zernike"):  # modules of this port alone
+    for own in ("ifta", "tolerance", "hankel", "modes", "pulse", "points", "zernike", "farfield"):  # modules of this port alone
         sys.modules[own] = importlib.import_module(f"{__name__}.{own}")
     for name in _ALIASES:
         mod = importlib.import_module(f"{__name__}.{name}")

@@ -65,6 +65,8 @@ EXPORTED = [
     "thz_rs_points_workspace_size", "thz_rs_points_forward", "thz_rs_points_adjoint",
     "thz_zernike_workspace_size", "thz_zernike_project", "thz_zernike_synthesize", "thz_zernike_table",
     "thz_unwrap_workspace_size", "thz_unwrap_phase", "thz_unwrap_residues",
+    "thz_farfield_workspace_size", "thz_farfield_list_forward", "thz_farfield_list_adjoint",
+    "thz_farfield_grid_forward", "thz_farfield_grid_adjoint", "thz_farfield_table",
     "thz_fft_rows",
     "thz_asm64_workspace_size", "thz_asm64_forward", "thz_czt64_workspace_size", "thz_czt64_forward",
     "thz_rsc64_workspace_size", "thz_rsc64_forward", "thz_fft64_rows",
@@ -409,6 +411,13 @@ class UnwrapDesc(ctypes.Structure):
                 ("anchor_col", ctypes.c_int), ("congruent", ctypes.c_int)]
 
 
+class FarfieldDesc(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("M", ctypes.c_int), ("Mu", ctypes.c_int), ("Mv", ctypes.c_int), ("obliquity", ctypes.c_int),
+                ("dx", ctypes.c_double), ("dy", ctypes.c_double), ("x0", ctypes.c_double), ("y0", ctypes.c_double),
+                ("scale", ctypes.c_double)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -565,6 +574,16 @@ def _declare(lib):
     lib.thz_unwrap_workspace_size.argtypes = [ud, ctypes.POINTER(c_size_t)]
     lib.thz_unwrap_phase.argtypes = [ud, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.thz_unwrap_residues.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    fd = ctypes.POINTER(FarfieldDesc)
+    lib.thz_farfield_workspace_size.argtypes = [fd, c_int, ctypes.POINTER(c_size_t)]
+    lib.thz_farfield_list_forward.argtypes = [fd, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.thz_farfield_list_adjoint.argtypes = [fd, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.thz_farfield_grid_forward.argtypes = [fd, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_void_p]
+    lib.thz_farfield_grid_adjoint.argtypes = [fd, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_void_p]
+    lib.thz_farfield_table.argtypes = [c_int, ctypes.c_double, ctypes.c_double, c_void_p, ctypes.c_longlong, c_int,
+                                       c_void_p, c_int, c_void_p, c_void_p]
     for tag, desc in (("asm64", AsmDesc64), ("czt64", CztDesc64), ("rsc64", RscDesc64)):
         getattr(lib, f"thz_{tag}_workspace_size").argtypes = [ctypes.POINTER(desc), ctypes.POINTER(c_size_t)]
         getattr(lib, f"thz_{tag}_forward").argtypes = [ctypes.POINTER(desc), c_void_p, c_void_p, c_void_p, c_size_t,
